@@ -7,8 +7,13 @@ passes (tg128).  Weights are synthetic (random valid quant blocks of the model's
 synthetic, everything resident in HBM before the timed region.  tok/s = tokens / time of that part, as llama-bench
 computes it; `value` is the tg128 rate (the HBM-bound mat-vec path), `pp512_tok_s` is reported beside it.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload NAME]
+    python bench.py [--gpus N --steps K --warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes runs of its own after
+the timed steps: the roofline legs (per-launch HIP events of both passes), the llama-bench protocol end to end through the
+reference's libllama with this module loaded (`e2e`) and the CPU baseline (`cpu_baseline`).  --dump-outputs DIR writes what
+the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 
 N > 1 = ggml row split: every weight's rows are sharded over the ranks (one process per GPU) and the partial
 results are concatenated with RCCL all-gather over xGMI after each MUL_MAT group ("scaling": "strong").
@@ -77,6 +82,104 @@ def roofline_leg(hp, q, n_batch, torch, n_outputs=None):
         e0, e1 = evs[key]
         agg[key] = [sum(i[1] for i in items), sum(i[2] for i in items), e0.elapsed_time(e1) * 1e-3, len(items)]
     return agg
+
+
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_ROWS = 64                 # token rows of a prompt-pass buffer written (a fixed seeded sample)
+
+
+def dump_outputs(hp, out_dir, n_prompt, n_out_pp, n_gen):
+    """--dump-outputs: the MUL_MAT outputs of the timed passes as they stand after the last step, i.e. what the path hands its
+    caller: one buffer per (matrix name, rows), which the last group that writes it owns (the last layer's products; the output
+    projection), for the prompt batch (`pp<n>_*`) and for token generation (`tg_*`; the prompt pass's one-row groups write there
+    too and are overwritten by the token passes).  Buffers no timed pass writes are left out; a row split writes the gathered
+    buffers.  Prompt-batch buffers are cut to DUMP_ROWS token rows chosen by a fixed seed (the same rows in every run and every
+    buffer), so the set stays under DUMP_MAX_BYTES; float32.  Inputs are seeded (HotPath's weights and activations), so two
+    builds can be compared file for file."""
+    import numpy as np
+    written = set()                             # (batch, buffer key) as HotPath.prepare keys its dst buffers
+    for grp in hp.wl.groups:
+        for m in grp.mats:
+            key = ("id", m.name.split(".")[-1], m.M) if m.n_expert else (m.name.split(".")[-1], hp.weights[m.name][0].shape[0])
+            written.add((n_out_pp if grp.outputs_only and n_out_pp is not None else n_prompt, key))
+            if n_gen > 0:
+                written.add((1, key))
+    bufs = []
+    for n in sorted(hp.io):
+        _, dst_local, dst_full, _ = hp.io[n]
+        for key, t in (dst_full if hp.split else dst_local).items():
+            if (n, key) in written:
+                bufs.append((("tg" if n == 1 else f"pp{n}") + "_" + "_".join(str(k) for k in key), n, t))
+    tg_bytes = sum(t.numel() * 4 for _, n, t in bufs if n == 1)
+    row_bytes = sum(t[0].numel() * 4 for _, n, t in bufs if n > 1)
+    n_rows = max(1, min(DUMP_ROWS, (DUMP_MAX_BYTES - tg_bytes) // max(row_bytes, 1)))
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, n, t in bufs:
+        a = t.float().cpu().numpy()
+        if n > 1:
+            a = a[np.sort(np.random.default_rng(0).choice(n, min(n, n_rows), replace=False))]
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float32))
+        total += a.nbytes
+    log(f"[bench] wrote {len(bufs)} output arrays ({total / 1e6:.1f} MB) to {out_dir}")
+
+
+def roofline_fields(hp, q, args, n_out_pp, torch):
+    """--full: the `roofline` (token generation, per kernel) and `roofline_pp` (prompt pass, per launch class) fields, from the
+    per-launch HIP-event legs (this rank's shard of the work)"""
+    agg1 = roofline_leg(hp, q, 1, torch)
+    aggp = roofline_leg(hp, q, args.n_prompt, torch, n_out_pp)
+    wl = hp.wl
+
+    # token generation: per kernel (a one-token group is ONE launch; buckets of different launch classes that ran the same kernel merge)
+    kern1 = by_kernel(agg1)
+    k1 = max(kern1, key=lambda k: kern1[k][2])
+    nb1, _, s1, calls1, launches1, classes1 = kern1[k1]
+    traffic, traffic_note = None, None
+    tf = ROOT / "profiles" / "pmc_traffic.json"
+    if tf.exists():
+        # HBM bytes per launch from the PMC passes (profiles/tools/pmc_traffic.sh: separate FETCH_SIZE / WRITE_SIZE passes over THIS
+        # leg's dispatch population, gfx950 corrections applied): taken only from a file that names this kernel and this workload
+        try:
+            tj = json.loads(tf.read_text())
+            if tj.get("label") == k1 and tj.get("workload") == wl.name:
+                traffic = tj.get("bytes_per_launch")
+                traffic_note = {"algo_bytes_per_launch_of_that_population": tj.get("algo_bytes_per_launch"), "ratio": tj.get("ratio"), "dispatches": tj.get("dispatches")}
+        except Exception:
+            traffic = None
+    roof = {"bound": "hbm", "kernel": "qmm::" + k1,
+            "achieved": round(nb1 / s1 / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(nb1 / s1 / 1e9 / HBM_PEAK_GBS, 4),
+            "traffic": traffic, "traffic_population": traffic_note, "launches": launches1, "launch_classes": sorted(set(classes1)),
+            "avg_launch_us": round(s1 / launches1 * 1e6, 2), "algo_bytes_per_launch": int(nb1 / launches1),
+            "all_tg_launches_GBs": round(sum(a[0] for a in agg1.values()) / sum(a[2] for a in agg1.values()) / 1e9, 1),
+            "kernels": {k: {"launches": v[4], "avg_launch_us": round(v[2] / v[4] * 1e6, 2), "GBs": round(v[0] / v[2] / 1e9, 1),
+                            "frac": round(v[0] / v[2] / 1e9 / HBM_PEAK_GBS, 4), "classes": sorted(set(v[5]))} for k, v in kern1.items()}}
+    # prompt pass: per launch class (qkv / wo / gate_up / down), each INCLUDING its prep_act and splitk_reduce launches; the groups
+    # llama-bench's prompt pass runs on one row (last layer's FFN, output projection) are mat-vec launches and listed apart
+    cls_pp = {}
+    for (cls, labels), (nb, fl, sec, cnt) in aggp.items():
+        batched = any(l.startswith(("mfma_", "prep_act")) for l in labels)
+        c = cls_pp.setdefault((cls, batched), {"flops": 0, "s": 0.0, "calls": 0, "launches": 0, "kernels": set()})
+        c["flops"] += fl; c["s"] += sec; c["calls"] += cnt; c["launches"] += cnt * len(labels); c["kernels"].update(labels)
+    pp_classes = {}
+    for (cls, batched), c in cls_pp.items():
+        if not batched:
+            continue
+        pp_classes[cls] = {"TFLOPs": round(c["flops"] / c["s"] / 1e12, 1), "frac": round(c["flops"] / c["s"] / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                           "us_per_call": round(c["s"] / c["calls"] * 1e6, 2), "calls": c["calls"], "launches_per_call": round(c["launches"] / c["calls"], 2),
+                           "share_of_pp_time": None, "kernels": sorted(c["kernels"])}
+    tot_pp_s = sum(c["s"] for (cls, batched), c in cls_pp.items())
+    for (cls, batched), c in cls_pp.items():
+        if batched:
+            pp_classes[cls]["share_of_pp_time"] = round(c["s"] / tot_pp_s, 4)
+    bat = [(k, c) for k, c in cls_pp.items() if k[1]]
+    flp, sp = sum(c["flops"] for _, c in bat), sum(c["s"] for _, c in bat)
+    (kp, _), cdom = max(bat, key=lambda kc: kc[1]["s"])
+    roof_pp = {"bound": "mfma", "kernel": "all batched launches of the prompt pass, each class with its prep_act / splitk_reduce launches",
+               "achieved": round(flp / sp / 1e12, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(flp / sp / 1e12 / MFMA_PEAK_TFLOPS, 4),
+               "dominant_class": kp, "classes": pp_classes}
+    return roof, roof_pp
 
 
 def by_kernel(agg):
@@ -241,14 +344,19 @@ def main():
     ap.add_argument("--workload", default=os.environ.get("QMM_WORKLOAD", "llama3-8b-q4_k_m"))
     ap.add_argument("--n-prompt", type=int, default=512)
     ap.add_argument("--n-gen", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end legs (llama-bench protocol through libllama: device and CPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the MUL_MAT outputs of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline legs, the end-to-end legs and the CPU baseline (off: the headline figures only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end legs (llama-bench protocol through libllama: device and CPU)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--wire-layout", action="store_true", help="keep Q4_0 / Q8_0 / Q6_K weights in GGUF wire layout (no planar repack, SURVEY 8f-2)")
     ap.add_argument("--chain", action="store_true", help="token generation as persistent chains (csrc/qmm_chain.hiph) instead of one launch per MUL_MAT group")
     ap.add_argument("--all-logits", action="store_true",
                     help="prompt pass with logits for every token (n_outputs = n_prompt) instead of llama-bench's last-token-only")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -355,6 +463,8 @@ def main():
         step(ev[i])
     barrier()
     wall = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(hp, args.dump_outputs, args.n_prompt, n_out_pp, args.n_gen)
 
     pp_s = sum(e[0].elapsed_time(e[1]) for e in ev) * 1e-3 / args.steps
     tg_s = sum(e[1].elapsed_time(e[2]) for e in ev) * 1e-3 / args.steps
@@ -365,58 +475,6 @@ def main():
 
     tg_tok_s = args.n_gen / tg_s
     pp_tok_s = args.n_prompt / pp_s
-
-    # ---- roofline leg: per-launch HIP events (this rank's shard of the work)
-    agg1 = roofline_leg(hp, q, 1, torch)
-    aggp = roofline_leg(hp, q, args.n_prompt, torch, n_out_pp)
-
-    # token generation: per kernel (a one-token group is ONE launch; buckets of different launch classes that ran the same kernel merge)
-    kern1 = by_kernel(agg1)
-    k1 = max(kern1, key=lambda k: kern1[k][2])
-    nb1, _, s1, calls1, launches1, classes1 = kern1[k1]
-    traffic, traffic_note = None, None
-    tf = ROOT / "profiles" / "pmc_traffic.json"
-    if tf.exists():
-        # HBM bytes per launch from the PMC passes (profiles/tools/pmc_traffic.sh: separate FETCH_SIZE / WRITE_SIZE passes over THIS
-        # leg's dispatch population, gfx950 corrections applied): taken only from a file that names this kernel and this workload
-        try:
-            tj = json.loads(tf.read_text())
-            if tj.get("label") == k1 and tj.get("workload") == wl.name:
-                traffic = tj.get("bytes_per_launch")
-                traffic_note = {"algo_bytes_per_launch_of_that_population": tj.get("algo_bytes_per_launch"), "ratio": tj.get("ratio"), "dispatches": tj.get("dispatches")}
-        except Exception:
-            traffic = None
-    roof = {"bound": "hbm", "kernel": "qmm::" + k1,
-            "achieved": round(nb1 / s1 / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(nb1 / s1 / 1e9 / HBM_PEAK_GBS, 4),
-            "traffic": traffic, "traffic_population": traffic_note, "launches": launches1, "launch_classes": sorted(set(classes1)),
-            "avg_launch_us": round(s1 / launches1 * 1e6, 2), "algo_bytes_per_launch": int(nb1 / launches1),
-            "all_tg_launches_GBs": round(sum(a[0] for a in agg1.values()) / sum(a[2] for a in agg1.values()) / 1e9, 1),
-            "kernels": {k: {"launches": v[4], "avg_launch_us": round(v[2] / v[4] * 1e6, 2), "GBs": round(v[0] / v[2] / 1e9, 1),
-                            "frac": round(v[0] / v[2] / 1e9 / HBM_PEAK_GBS, 4), "classes": sorted(set(v[5]))} for k, v in kern1.items()}}
-    # prompt pass: per launch class (qkv / wo / gate_up / down), each INCLUDING its prep_act and splitk_reduce launches; the groups
-    # llama-bench's prompt pass runs on one row (last layer's FFN, output projection) are mat-vec launches and listed apart
-    cls_pp = {}
-    for (cls, labels), (nb, fl, sec, cnt) in aggp.items():
-        batched = any(l.startswith(("mfma_", "prep_act")) for l in labels)
-        c = cls_pp.setdefault((cls, batched), {"flops": 0, "s": 0.0, "calls": 0, "launches": 0, "kernels": set()})
-        c["flops"] += fl; c["s"] += sec; c["calls"] += cnt; c["launches"] += cnt * len(labels); c["kernels"].update(labels)
-    pp_classes = {}
-    for (cls, batched), c in cls_pp.items():
-        if not batched:
-            continue
-        pp_classes[cls] = {"TFLOPs": round(c["flops"] / c["s"] / 1e12, 1), "frac": round(c["flops"] / c["s"] / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                           "us_per_call": round(c["s"] / c["calls"] * 1e6, 2), "calls": c["calls"], "launches_per_call": round(c["launches"] / c["calls"], 2),
-                           "share_of_pp_time": None, "kernels": sorted(c["kernels"])}
-    tot_pp_s = sum(c["s"] for (cls, batched), c in cls_pp.items())
-    for (cls, batched), c in cls_pp.items():
-        if batched:
-            pp_classes[cls]["share_of_pp_time"] = round(c["s"] / tot_pp_s, 4)
-    bat = [(k, c) for k, c in cls_pp.items() if k[1]]
-    flp, sp = sum(c["flops"] for _, c in bat), sum(c["s"] for _, c in bat)
-    (kp, _), cdom = max(bat, key=lambda kc: kc[1]["s"])
-    roof_pp = {"bound": "mfma", "kernel": "all batched launches of the prompt pass, each class with its prep_act / splitk_reduce launches",
-               "achieved": round(flp / sp / 1e12, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(flp / sp / 1e12 / MFMA_PEAK_TFLOPS, 4),
-               "dominant_class": kp, "classes": pp_classes}
 
     out = {
         "metric": "llama-bench pp512 & tg128 tok/s over the offloaded quantized MUL_MAT/MUL_MAT_ID path (value = tg128)",
@@ -435,9 +493,11 @@ def main():
         "tg_ms_per_token": round(tg_s / args.n_gen * 1e3, 4), "pp_ms_per_batch": round(pp_s * 1e3, 3),
         "tg_algo_GBs": round(wl.algo_bytes(1) / world / (tg_s / args.n_gen) / 1e9, 1),
         "pp_algo_TFLOPs": round(wl.flops(args.n_prompt, n_out_pp) / world / pp_s / 1e12, 1),
-        "roofline": roof, "roofline_pp": roof_pp,
     }
-    if rank == 0 and world == 1 and not args.no_e2e:
+    # ---- --full only: the roofline legs, the end-to-end legs, the CPU baseline
+    if args.full:
+        out["roofline"], out["roofline_pp"] = roofline_fields(hp, q, args, n_out_pp, torch)
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         lb = LlamaBench(wl.name)
         try:
             cores = min(len(os.sched_getaffinity(0)), 64)

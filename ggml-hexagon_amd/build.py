@@ -11,6 +11,10 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 QMM_SO = PKG / "libggml_mi355x_qmm.so"
 PLUGIN_SO = PKG / "libggml-mi355x.so"
+# a copy of the plugin kept with the other binaries built from the ggml tree (oracle/_ref, never in git): a checkout on a
+# machine without that tree takes the module from there.  A directory of its own: next to the reference's executables it
+# would sit where ggml looks for backend modules by name
+PLUGIN_PREBUILT = ROOT / "oracle" / "_ref" / "plugin" / "libggml-mi355x.so"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 GGML_SRC = Path(os.environ.get("GGML_SRC_DIR", "/root/reference/ggml"))
 
@@ -52,8 +56,9 @@ def have_ggml_headers() -> bool:
 
 def build_plugin(force: bool = False) -> Path | None:
     """the ggml backend plugin (GGML_BACKEND_DL module).  It is compiled against the ggml headers of the
-    llama.cpp tree it will be loaded into (here: the reference tree, in place); when that tree is not
-    present the prebuilt module, if any, is kept."""
+    llama.cpp tree it will be loaded into (here: the reference tree, in place) and a copy is kept in
+    oracle/_ref/plugin; when that tree is not present the module is taken from that copy (it finds the kernel
+    library next to itself, rpath $ORIGIN), or the module already in place, if any, is kept."""
     src = CSRC / "ggml-mi355x.cpp"
     if not src.exists():
         return None
@@ -61,6 +66,8 @@ def build_plugin(force: bool = False) -> Path | None:
     if not force and _newer(PLUGIN_SO, srcs + [QMM_SO]):
         return PLUGIN_SO
     if not have_ggml_headers() or not (shutil.which("g++") or shutil.which("c++")):
+        if PLUGIN_PREBUILT.exists() and (not PLUGIN_SO.exists() or PLUGIN_PREBUILT.stat().st_mtime > PLUGIN_SO.stat().st_mtime):
+            shutil.copy2(PLUGIN_PREBUILT, PLUGIN_SO)
         return PLUGIN_SO if PLUGIN_SO.exists() else None
     cxx = shutil.which("g++") or shutil.which("c++")
     cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-DGGML_BACKEND_DL", "-DGGML_BACKEND_BUILD",
@@ -68,6 +75,8 @@ def build_plugin(force: bool = False) -> Path | None:
            f"-I{GGML_SRC / 'include'}", f"-I{GGML_SRC / 'src'}", f"-I{ROOT / 'include'}",
            str(src), "-o", str(PLUGIN_SO), f"-L{PKG}", "-lggml_mi355x_qmm", "-Wl,-rpath,$ORIGIN"]
     subprocess.run(cmd, check=True)
+    PLUGIN_PREBUILT.parent.mkdir(parents=True, exist_ok=True)
+    shutil.copy2(PLUGIN_SO, PLUGIN_PREBUILT)
     return PLUGIN_SO
 
 

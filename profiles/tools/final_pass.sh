@@ -7,10 +7,10 @@ ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=$ROOT/gpurun_out/final
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-echo "== bench (plain, with cpu_baseline and e2e)"
-timeout -k 10 600 python3 $ROOT/bench.py --steps 3 > $OUT/bench.json 2> $OUT/bench.err; echo rc=$?
+echo "== bench --full (with roofline, cpu_baseline and e2e)"
+timeout -k 10 600 python3 $ROOT/bench.py --steps 3 --full > $OUT/bench.json 2> $OUT/bench.err; echo rc=$?
 echo "== rocprofv3 kernel trace of the hot-path bench"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o b -- python3 $ROOT/bench.py --no-e2e --no-cpu-baseline --steps 2 > $OUT/prof_bench.log 2>&1; echo rc=$?
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_bench -o b -- python3 $ROOT/bench.py --full --no-e2e --no-cpu-baseline --steps 2 > $OUT/prof_bench.log 2>&1; echo rc=$?
 python3 $ROOT/profiles/kernel_shapes.py $OUT/prof_bench/b_kernel_trace.csv > $OUT/kernel_shapes.csv 2>/dev/null
 echo "== rocprofv3 kernel traces of end-to-end token generation and prompt processing (libllama + plugin), llama-bench's two tests"
 export GGML_BACKEND_PATH=$ROOT/ggml-hexagon_amd/libggml-mi355x.so LD_LIBRARY_PATH=$ROOT/oracle/_ref:$LD_LIBRARY_PATH

@@ -218,6 +218,39 @@ def test_hotpath_rowsplit_world2_gloo():
     assert res == [(0, True), (1, True)], res
 
 
+def test_bench_dump_outputs_writes_what_the_passes_computed(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on the CPU stand-in: every dst buffer the timed passes write and none they leave alone (the prompt
+    batch's output projection when one row wants logits), prompt-batch buffers cut to the same seeded rows, float32, under the
+    64 MB cap, and the same files from two runs on the same seeds"""
+    import torch
+    import bench
+    from ggml_hexagon_amd import synth, workload
+    from ggml_hexagon_amd.hotpath import HotPath
+    monkeypatch.setattr(synth, "synth_weights_torch", lambda t, rows, k, device, seed=0, sigma=0.02:
+                        torch.from_numpy(synth.synth_weights(t, rows, k, seed=seed, sigma=0.2)))
+    wl = workload._llama("toy", 2, 256, 512, 4, 2, 1000, "q4_k_m")
+    dumps = []
+    for run in range(2):
+        hp = HotPath(_OracleQmm(), wl, torch.device("cpu"), seed=5)
+        hp.run(100, 1)                      # a prompt batch that wants one row of logits, then a token
+        hp.run(1)
+        bench.dump_outputs(hp, tmp_path / str(run), 100, 1, 1)
+        dumps.append({f.name: np.load(f) for f in sorted((tmp_path / str(run)).iterdir())})
+    a, b = dumps
+    names = ("attn_q_256", "attn_k_128", "attn_v_128", "attn_output_256", "ffn_gate_512", "ffn_up_512", "ffn_down_256")
+    assert set(a) == {f"pp100_{n}.npy" for n in names} | {f"tg_{n}.npy" for n in names + ("output_1000",)}
+    rows = np.sort(np.random.default_rng(0).choice(100, bench.DUMP_ROWS, replace=False))
+    _, pp_dst, _, _ = hp.io[100]
+    _, tg_dst, _, _ = hp.io[1]
+    for name, arr in a.items():
+        assert arr.dtype == np.float32 and np.array_equal(arr, b[name]), name
+        stage, rest = name[:-4].split("_", 1)
+        key = (rest.rsplit("_", 1)[0], int(rest.rsplit("_", 1)[1]))
+        want = pp_dst[key].numpy()[rows] if stage == "pp100" else tg_dst[key].numpy()
+        assert np.array_equal(arr, want), name
+    assert sum(arr.nbytes for arr in a.values()) <= bench.DUMP_MAX_BYTES
+
+
 def test_prompt_pass_counts_output_rows_only():
     """llama-bench's prompt test wants one row of logits: the last layer's FFN and the output projection run at
     n_outputs = 1 (workload.Group.outputs_only), everything else at n_prompt"""

@@ -28,11 +28,11 @@ def _libs():
 
 @pytest.fixture(scope="module")
 def env():
-    if not (Path("/root/reference/ggml/include/ggml-backend.h").exists() or MOD.exists()):
+    # oracle/Makefile builds (or refreshes) the module where the reference tree is present and leaves it alone elsewhere
+    subprocess.run(["make", "-C", str(ROOT / "oracle"), "-j8", "ref"], check=True, capture_output=True)
+    subprocess.run(["make", "-C", str(ROOT / "oracle"), "asan"], check=True, capture_output=True)
+    if not MOD.exists():
         pytest.skip("needs the reference tree (ggml headers) to build the sanitizer module")
-    if Path("/root/reference/ggml/include/ggml-backend.h").exists():
-        subprocess.run(["make", "-C", str(ROOT / "oracle"), "-j8", "ref"], check=True, capture_output=True)
-        subprocess.run(["make", "-C", str(ROOT / "oracle"), "asan"], check=True, capture_output=True)
     return dict(os.environ, LD_PRELOAD=_libs(), ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
                 GGML_BACKEND_PATH=str(MOD), QMM_FUZZ_PLAN_ONLY="1")
 
