@@ -59,10 +59,11 @@ def build_plugin(force: bool = False) -> Path | None:
     llama.cpp tree it will be loaded into (here: the reference tree, in place) and a copy is kept in
     oracle/_ref/plugin; when that tree is not present the module is taken from that copy (it finds the kernel
     library next to itself, rpath $ORIGIN), or the module already in place, if any, is kept."""
-    src = CSRC / "ggml-mi355x.cpp"
+    src = CSRC / "ggml-mi355x.cpp"              # one translation unit: it includes the other sections (mi355x_*.cpp, one per concern)
     if not src.exists():
         return None
-    srcs = [src, ROOT / "include" / "ggml-mi355x.h", ROOT / "include" / "ggml_mi355x_qmm.h", ROOT / "include" / "ggml_mi355x_ops.h"]
+    srcs = [src] + sorted(CSRC.glob("mi355x_*")) + [CSRC / "qmm_switches.h",
+                    ROOT / "include" / "ggml-mi355x.h", ROOT / "include" / "ggml_mi355x_qmm.h", ROOT / "include" / "ggml_mi355x_ops.h"]
     if not force and _newer(PLUGIN_SO, srcs + [QMM_SO]):
         return PLUGIN_SO
     if not have_ggml_headers() or not (shutil.which("g++") or shutil.which("c++")):

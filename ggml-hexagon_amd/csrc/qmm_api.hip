@@ -300,42 +300,26 @@ qmm_ctx * qmm_create(int device) {
         }
     }
     (void) hipGetLastError();
-    const char * e = getenv("GGML_MI355X_SPLITK");
-    if (e) c->splitk = atoi(e);
-    e = getenv("GGML_MI355X_ACT_MODE");
-    if (e) c->act_mode = atoi(e) ? QMM_ACT_X86 : QMM_ACT_REF;
-    e = getenv("GGML_MI355X_MV_KMIX");      // 0: off, 1: K-quant groups only, 2 (default): also groups with Q8_0 matrices
-    if (e) c->mv_kmix = atoi(e);
-    e = getenv("GGML_MI355X_WIDE");
-    if (e) c->wide = atoi(e);
-    e = getenv("GGML_MI355X_R64");
-    if (e) c->r64 = atoi(e);
-    e = getenv("GGML_MI355X_R64S");
-    if (e) c->r64s = atoi(e);
-    e = getenv("GGML_MI355X_PREP_REG");
-    if (e) c->prep_reg = atoi(e);
-    e = getenv("GGML_MI355X_REGB_Q23");
-    if (e) c->regb_q23 = atoi(e) != 0;
-    e = getenv("GGML_MI355X_MV_ONEPASS");
-    if (e) c->mv_onepass = atoi(e);
-    e = getenv("GGML_MI355X_SIDE");
-    if (e) c->side_on = atoi(e);
-    e = getenv("GGML_MI355X_SPLITK_COMBINE");
-    if (e) c->splitk_combine = atoi(e);
-    e = getenv("GGML_MI355X_CHAIN");
-    if (e) c->chain_enabled = atoi(e);
-    e = getenv("GGML_MI355X_MV_BPC");
-    if (e && atoi(e) >= 1 && atoi(e) <= 8) c->mv_bpc = atoi(e);
-    e = getenv("GGML_MI355X_MM_GROUP");
-    if (e) c->mm_group = atoi(e);
-    e = getenv("GGML_MI355X_SKINNY");
-    if (e) c->skinny = atoi(e);
-    e = getenv("GGML_MI355X_SKINNY_MAXN");
-    if (e && atoi(e) >= 9) c->skinny_max_n = c->skinny_max_n_few = atoi(e);
-    e = getenv("GGML_MI355X_ABLATE");
-    if (e) { int v = atoi(e); (void) hipMemcpyToSymbol(HIP_SYMBOL(g_mfma_dbg), &v, sizeof(int)); }
-    e = getenv("GGML_MI355X_PREC");
-    if (e) c->prec = (!strcmp(e, "bf16") || !strcmp(e, "0")) ? QMM_PREC_BF16 : QMM_PREC_F16_Q8;
+    // the environment switches (qmm_switches.h), read for every context
+    const qmm_sw::values sw = qmm_sw::read();
+    c->splitk         = sw[qmm_sw::SW_SPLITK];
+    c->act_mode       = sw[qmm_sw::SW_ACT_MODE] ? QMM_ACT_X86 : QMM_ACT_REF;
+    c->mv_kmix        = sw[qmm_sw::SW_MV_KMIX];
+    c->wide           = sw[qmm_sw::SW_WIDE];
+    c->r64            = sw[qmm_sw::SW_R64];
+    c->r64s           = sw[qmm_sw::SW_R64S];
+    c->prep_reg       = sw[qmm_sw::SW_PREP_REG];
+    c->regb_q23       = sw[qmm_sw::SW_REGB_Q23] != 0;
+    c->mv_onepass     = sw[qmm_sw::SW_MV_ONEPASS];
+    c->side_on        = sw[qmm_sw::SW_SIDE];
+    c->splitk_combine = sw[qmm_sw::SW_SPLITK_COMBINE];
+    c->chain_enabled  = sw.is_set(qmm_sw::SW_CHAIN) ? sw[qmm_sw::SW_CHAIN] : 1;      // (the table's default is the plugin's: no chains unless asked)
+    c->mv_bpc         = sw[qmm_sw::SW_MV_BPC];
+    c->mm_group       = sw[qmm_sw::SW_MM_GROUP];
+    c->skinny         = sw[qmm_sw::SW_SKINNY];
+    if (sw[qmm_sw::SW_SKINNY_MAXN]) c->skinny_max_n = c->skinny_max_n_few = sw[qmm_sw::SW_SKINNY_MAXN];
+    if (sw.is_set(qmm_sw::SW_ABLATE)) { int v = sw[qmm_sw::SW_ABLATE]; (void) hipMemcpyToSymbol(HIP_SYMBOL(g_mfma_dbg), &v, sizeof(int)); }
+    c->prec           = qmm_sw::prec_is_bf16(sw.str(qmm_sw::SW_PREC)) ? QMM_PREC_BF16 : QMM_PREC_F16_Q8;
     return c;
 }
 
@@ -540,7 +524,7 @@ int qmm_synchronize(qmm_ctx * c, void * st) {
             const int zero = 0;
             HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_mfma_nonfinite), &zero, sizeof(int)));
             return fail(QMM_EUNSUPPORTED, "prefill (f16 on Q8 activations) produced non-finite values: a weight block exceeds the f16 range (|w| >= 65504) "
-                                          "or the activations are not finite; use QMM_PREC_BF16 (GGML_MI355X_PREC=bf16) for this model");
+                                          "or the activations are not finite; use QMM_PREC_BF16 (" QMM_SWITCH_ENV(PREC) "=bf16) for this model");
         }
     }
     if (c->id_calls != c->id_checked) {                      // MUL_MAT_ID launches since the last look: did a kernel meet an expert id out of range?

@@ -38,7 +38,7 @@ std::mutex g_rccl_mu;
 int load_rccl() {
     std::lock_guard<std::mutex> lk(g_rccl_mu);
     if (g_rccl.lib) return QMM_OK;
-    const char * names[] = { getenv("GGML_MI355X_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" };
+    const char * names[] = { qmm_sw::read_str(qmm_sw::SW_RCCL_LIB), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" };
     void * h = nullptr;
     for (const char * n : names)
         if (n && *n && (h = dlopen(n, RTLD_NOW | RTLD_LOCAL))) break;

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "../../include/ggml_mi355x_qmm.h"
+#include "qmm_switches.h"
 
 #include <hip/hip_runtime.h>
 

@@ -2130,7 +2130,7 @@ int qmm_op_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * a, const qmm_tensor * 
 }
 
 static bool attn_short_on() {                            // GGML_MI355X_ATTN_SHORT=0: the general kernel at every n_kv (A/B runs)
-    static const bool on = [] { const char * e = getenv("GGML_MI355X_ATTN_SHORT"); return !(e && atoi(e) == 0); }();
+    static const bool on = qmm_sw::read_one(qmm_sw::SW_ATTN_SHORT) != 0;
     return on;
 }
 
@@ -2162,7 +2162,7 @@ int qmm_attn_decode(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * k, c
     const dim3 grid((unsigned) g.H, (unsigned) q->ne[1]);
     const size_t lds = (size_t) g.n_kv * 4;
     hipStream_t st = ctx->s(stream);
-    static const bool split_on = [] { const char * e = getenv("GGML_MI355X_ATTN_SPLIT"); return !(e && atoi(e) == 0); }();
+    static const bool split_on = qmm_sw::read_one(qmm_sw::SW_ATTN_SPLIT) != 0;
     if (split_on && g.n_kv >= 1024 && g.D <= 128) {
         // kv range over S workgroups per (head, token), then the merge (long caches: one workgroup per head is latency-bound)
         const int S = g.n_kv / 256 < 16 ? g.n_kv / 256 : 16;

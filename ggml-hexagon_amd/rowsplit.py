@@ -7,7 +7,7 @@ every rank computes dst[:, row_low:row_high] and the slices are gathered over RC
 """
 from __future__ import annotations
 
-ROW_ROUNDING = 256       # the prefill kernels' row tile and the plugin's SPLIT_ROW_ROUNDING (ggml-mi355x.cpp): a slice never starts inside a 256-row tile
+ROW_ROUNDING = 256       # the prefill kernels' row tile and the plugin's SPLIT_ROW_ROUNDING (mi355x_split.cpp): a slice never starts inside a 256-row tile
 
 
 def rounding_for(nrows: int, world: int, rounding: int = ROW_ROUNDING) -> int:

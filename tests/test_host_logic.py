@@ -322,3 +322,110 @@ def test_glue_op_surface_predicates():
     out = T.make(F32, [4096, 1])
     assert lib.qmm_attn_decode_supported(r(q1), r(k), r(v), r(m1), r(out)) == 1
     assert lib.qmm_attn_decode_supported(r(qp), r(k), r(v), r(T.make(F32, [640, 512])), r(T.make(F32, [4096, 512]))) == 0      # prefill batch
+
+
+# ---- the switch table (csrc/qmm_switches.h): the one list of GGML_MI355X_* environment switches
+
+SWITCH_HEADER = ROOT / "ggml-hexagon_amd" / "csrc" / "qmm_switches.h"
+# name -> (kind, value with the variable unset), read off qmm_create, qmm_ops.hip, qmm_comm.hip and the plugin as they were before the
+# table existed.  STR switches have no number: None.  SKINNY_MAXN 0 = the built-in bounds (64, and 128 for matrices with few row
+# groups); CHAIN 0 is the plugin's default (the library's qmm_chain_begin records unless CHAIN=0 is set: test_gpu_chain.py).
+SWITCH_DEFAULTS = {
+    "PREC": ("STR", None), "ACT_MODE": ("ATOI", 0), "SPLITK": ("ATOI", 1), "SPLITK_COMBINE": ("ATOI", 0), "SKINNY": ("ATOI", 1),
+    "SKINNY_MAXN": ("ATOI", 0), "MM_GROUP": ("ATOI", 1), "MV_KMIX": ("ATOI", 2), "MV_BPC": ("ATOI", 1), "MV_ONEPASS": ("ATOI", 1),
+    "REGB_Q23": ("ATOI", 1), "WIDE": ("ATOI", 1), "R64": ("ATOI", 2), "R64S": ("ATOI", 1), "PREP_REG": ("ATOI", 1), "SIDE": ("ATOI", 0),
+    "ABLATE": ("ATOI", 0), "ATTN_SHORT": ("OFF0", 1), "ATTN_SPLIT": ("OFF0", 1), "RCCL_LIB": ("STR", None), "CHAIN": ("ATOI", 0),
+    "GLUE": ("OFF0", 1), "FUSE": ("OFF0", 1), "ATTN_ROPE": ("OFF0", 1), "REPACK": ("OFF0", 1), "STAGED_SET": ("OFF0", 1),
+    "RCCL": ("ATOI", 0), "TIMING": ("ATOI", 0), "NO_PINNED": ("PRESENT", 0), "DEBUG": ("PRESENT", 0), "VIRTUAL_DEVICES": ("STR", None),
+    "ROUTER_NORM_OFF": ("PRESENT", 0), "PREP_NORM_OFF": ("PRESENT", 0), "ROUTER_LOGITS_OFF": ("PRESENT", 0),
+    "MOE_SWIGLU_OFF": ("PRESENT", 0), "MOE_COMBINE_NORM_OFF": ("PRESENT", 0),
+}
+SWITCH_PROBE = r"""
+#include "qmm_switches.h"
+#include <cstdio>
+int main(int argc, char **) {
+    using namespace qmm_sw;
+    static const char * kinds[] = { "ATOI", "OFF0", "PRESENT", "STR" };
+    const values v = read();
+    for (int i = 0; i < SW_COUNT; ++i) {
+        if (argc > 1) printf("%s %s %d\n", table[i].name, kinds[table[i].k], table[i].def);
+        else printf("%s %d %d %s\n", table[i].name, v[(id) i], (int) v.is_set((id) i), v.str((id) i) ? v.str((id) i) : "(null)");
+    }
+    if (argc == 1) printf("prec_is_bf16 %d\n", (int) prec_is_bf16(v.str(SW_PREC)));
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def switch_probe(tmp_path_factory):
+    """the header alone, compiled by the host compiler (no HIP, no ggml) into a program that prints the table / one reading of the environment"""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    d = tmp_path_factory.mktemp("switches")
+    (d / "probe.cpp").write_text(SWITCH_PROBE)
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", f"-I{SWITCH_HEADER.parent}", str(d / "probe.cpp"), "-o", str(d / "probe")], check=True)
+
+    def run(env=None, table=False):
+        base = {k: v for k, v in os.environ.items() if not k.startswith("GGML_MI355X_")}
+        out = subprocess.run([str(d / "probe")] + (["table"] if table else []), env=dict(base, **{f"GGML_MI355X_{k}": v for k, v in (env or {}).items()}),
+                             check=True, capture_output=True, text=True).stdout
+        return {l.split()[0].replace("GGML_MI355X_", ""): l.split()[1:] for l in out.splitlines()}
+    return run
+
+
+def test_switch_table_keeps_every_name_kind_and_default(switch_probe):
+    table = switch_probe(table=True)
+    assert len(table) == 36 and set(table) == set(SWITCH_DEFAULTS)
+    unset = switch_probe()
+    for name, (kind, default) in SWITCH_DEFAULTS.items():
+        assert table[name][0] == kind, name
+        assert unset[name][1:] == ["0", "(null)"], name                  # not set, no text
+        if kind != "STR":
+            assert int(unset[name][0]) == default, name
+            assert int(table[name][1]) == default, name
+    assert unset["prec_is_bf16"] == ["0"]                                  # f16 on Q8 activations unless asked
+
+
+def test_switch_parse_rules(switch_probe):
+    val = lambda env, name: int(switch_probe(env)[name][0])
+    # value by atoi
+    assert val({"R64": "3"}, "R64") == 3 and val({"SPLITK": "0"}, "SPLITK") == 0 and val({"TIMING": "1"}, "TIMING") == 1
+    assert val({"MV_KMIX": "junk"}, "MV_KMIX") == 0                                              # atoi of no number
+    # off only when set to 0
+    for name in ("ATTN_SHORT", "ATTN_SPLIT", "GLUE", "FUSE", "ATTN_ROPE", "REPACK", "STAGED_SET"):
+        assert val({name: "0"}, name) == 0 and val({name: "1"}, name) == 1 and val({name: "2"}, name) == 1, name
+        assert val({name: ""}, name) == 0 and val({name: "off"}, name) == 0, name               # atoi == 0
+    # on by mere presence, "0" included
+    for name in ("DEBUG", "NO_PINNED", "ROUTER_NORM_OFF", "PREP_NORM_OFF", "ROUTER_LOGITS_OFF", "MOE_SWIGLU_OFF", "MOE_COMBINE_NORM_OFF"):
+        assert val({name: "1"}, name) == 1 and val({name: "0"}, name) == 1 and val({name: ""}, name) == 1, name
+    # validity: MV_BPC only in 1..8, SKINNY_MAXN only from 9 up; anything else leaves the default
+    assert [val({"MV_BPC": v}, "MV_BPC") for v in ("0", "1", "4", "8", "9", "-2")] == [1, 1, 4, 8, 1, 1]
+    assert [val({"SKINNY_MAXN": v}, "SKINNY_MAXN") for v in ("8", "9", "96", "0", "-1")] == [0, 9, 96, 0, 0]
+    # strings: the text as it is; PREC is bf16 for "bf16" or "0" and f16 on Q8 for anything else
+    r = switch_probe({"PREC": "bf16", "RCCL_LIB": "/x/librccl.so", "VIRTUAL_DEVICES": "2"})
+    assert r["PREC"][1:] == ["1", "bf16"] and r["RCCL_LIB"][2] == "/x/librccl.so" and r["VIRTUAL_DEVICES"][2] == "2"
+    assert [switch_probe({"PREC": v})["prec_is_bf16"] for v in ("bf16", "0", "f16q8", "1", "BF16", "")] == [["1"], ["1"], ["0"], ["0"], ["0"], ["0"]]
+    # a switch that is set reports it (the library's CHAIN and ABLATE act only then)
+    assert switch_probe({"CHAIN": "0"})["CHAIN"][:2] == ["0", "1"] and switch_probe({"ABLATE": "5"})["ABLATE"][:2] == ["5", "1"]
+
+
+def test_every_switch_is_documented():
+    text = (ROOT / "INTEGRATION.md").read_text()
+    for name in SWITCH_DEFAULTS:
+        assert re.search(rf"`GGML_MI355X_{name}\b", text), f"GGML_MI355X_{name} is not in INTEGRATION.md"
+
+
+def test_switch_names_live_in_the_header_only():
+    """no GGML_MI355X_* environment name as a string literal anywhere else in csrc/ (comments may speak of them; the public macros
+    GGML_MI355X_BACKEND_NAME / _MAX_DEVICES are not strings), and no getenv outside the header"""
+    for f in sorted((ROOT / "ggml-hexagon_amd" / "csrc").iterdir()):
+        if f == SWITCH_HEADER or f.suffix not in (".cpp", ".h", ".hip", ".hiph"):
+            continue
+        for n, line in enumerate(f.read_text().splitlines(), 1):
+            code = re.sub(r"//.*$", "", line)
+            assert not re.search(r'"(?:[^"\\]|\\.)*GGML_MI355X_', code), f"{f.name}:{n}: {line.strip()[:120]}"
+            assert "getenv" not in code, f"{f.name}:{n}: {line.strip()[:120]}"
