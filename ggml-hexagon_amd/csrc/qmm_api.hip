@@ -721,30 +721,40 @@ static int mul_mat_group_impl(qmm_ctx * c, const qmm_weight * ws, int nw, int64_
     }
     c->mfma_calls++;
     // The group shares src1: its 16-bit operand is prepared once per activation format (key).  Runs of same-type matrices are one tiled
-    // launch each where the shapes allow (mfma_mul_mat_group).  A run with a NEW key has nothing in common with what was issued before
+    // launch each where the shapes allow (the run's plan, qmm_prefill_plan.h).  A run with a NEW key has nothing in common with what was issued before
     // it except src1: it goes to a side stream (own workspace slice) between a fork and a join event, so that its prep / MFMA / reduce
     // launches overlap the earlier runs' instead of queueing behind them; a run that reuses a prep stays on that prep's stream.
-    struct Run { int i, j, key, lane; };
+    struct Run { int i, j, lane; PrefillPlan plan; };
     Run runs[MV_MAX_GROUP * 2];
     int nruns = 0;
+    const PrefillRules rules = prefill_rules(c);
     for (int i = 0; i < nw;) {
         if (ws[i].M == 0) { ++i; continue; }
+        int64_t M[4] = { ws[i].M };
+        const int key = prefill_prep_key(rules, ws[i].type, ws[i].M, K, N);
         int j = i + 1;
-        while (j < nw && j - i < 4 && ws[j].type == ws[i].type && ws[j].M > 0) ++j;
-        const int key = mfma_prep_key(c, ws[i].type, N, ws[i].M, K);
-        bool same_key = true;
-        for (int k = i + 1; k < j; ++k) same_key = same_key && mfma_prep_key(c, ws[k].type, N, ws[k].M, K) == key;
-        if (!same_key) j = i + 1;
+        while (j < nw && j - i < 4 && ws[j].type == ws[i].type && ws[j].M > 0) { M[j - i] = ws[j].M; ++j; }
+        for (int k = i + 1; k < j; ++k) if (prefill_prep_key(rules, ws[k].type, ws[k].M, K, N) != key) j = i + 1;
         if (nruns == (int) (sizeof(runs) / sizeof(runs[0]))) return fail(QMM_EUNSUPPORTED, "qmm_mul_mat_group: too many runs in one group");
-        runs[nruns++] = { i, j, key, 0 };
+        runs[nruns++] = { i, j, 0, prefill_plan(rules, ws[i].type, M, j - i, K, N, 1, prefill_flags(c)) };
         i = j;
     }
     int nlanes = 1;                                              // lane 0 = the caller's stream, 1..3 = side streams
     const bool side = c->side_on && nruns > 1 && !c->prep_x2;
     for (int r = 1; r < nruns; ++r) {
         int found = -1;
-        for (int q = 0; q < r; ++q) if (runs[q].key == runs[r].key) found = runs[q].lane;      // reuses that run's prep: same stream, behind it
+        for (int q = 0; q < r; ++q) if (runs[q].plan.key == runs[r].plan.key) found = runs[q].lane;      // reuses that run's prep: same stream, behind it
         runs[r].lane = found >= 0 ? found : (side && nlanes < 4 ? nlanes++ : 0);
+    }
+    // disjoint workspace slices, each as large as the largest plan of its lane's runs (they follow each other on the lane's stream and share
+    // the operand); all of it allocated before the first launch, so that no run moves the workspace under a prepared operand
+    size_t lane_base[4] = { 0, 0, 0, 0 };
+    {
+        size_t lane_bytes[4] = { 0, 0, 0, 0 }, base = 0;
+        for (int r = 0; r < nruns; ++r) lane_bytes[runs[r].lane] = std::max(lane_bytes[runs[r].lane], runs[r].plan.ws_total);
+        for (int l = 0; l < nlanes; ++l) { lane_base[l] = base; base += (lane_bytes[l] + 255) & ~(size_t) 255; }
+        const int rc = ensure_ws(c, base);
+        if (rc) return rc;
     }
     if (nlanes > 1) {
         for (int l = 1; l < nlanes; ++l) {
@@ -755,17 +765,6 @@ static int mul_mat_group_impl(qmm_ctx * c, const qmm_weight * ws, int nw, int64_
         HIP_TRY(hipEventRecord(c->ev_fork, st));
         for (int l = 1; l < nlanes; ++l) HIP_TRY(hipStreamWaitEvent(c->side[l - 1], c->ev_fork, 0));
     }
-    // disjoint workspace slices, sized up front by what a lane's runs can take at most (operand + scales + 8 split-K slabs of its rows)
-    size_t lane_base[4] = { 0, 0, 0, 0 };
-    {
-        const size_t fixed = (size_t) mfma_npad(N) * mfma_kpad(K) * 2 + (((size_t) mfma_npad(N) * 4 + 255) & ~(size_t) 255) + 1024;
-        size_t rows[4] = { 0, 0, 0, 0 };
-        for (int r = 0; r < nruns; ++r)
-            for (int k = runs[r].i; k < runs[r].j; ++k) rows[runs[r].lane] += (size_t) ws[k].M;
-        size_t base = 0;
-        for (int l = 0; l < nlanes; ++l) { lane_base[l] = base; base += (fixed + 8 * (size_t) N * rows[l] * sizeof(float) + 255) & ~(size_t) 255; }
-        if (nlanes == 1) lane_base[0] = 0;
-    }
     int lane_key[4] = { -1, -1, -1, -1 };
     int rc = QMM_OK;
     // side lanes first: their (small) launches are in the queues when the caller's stream starts on the big run
@@ -775,10 +774,8 @@ static int mul_mat_group_impl(qmm_ctx * c, const qmm_weight * ws, int nw, int64_
             if ((pass == 0) != (R.lane != 0)) continue;
             c->ws_base = lane_base[R.lane];
             hipStream_t ls = R.lane ? c->side[R.lane - 1] : st;
-            const bool reuse = R.key == lane_key[R.lane];
-            rc = R.j - R.i > 1 ? mfma_mul_mat_group(c, ls, ws[R.i].type, ws + R.i, R.j - R.i, K, x, N, ldx, reuse)
-                               : mfma_mul_mat(c, ls, ws[R.i].type, ws[R.i].w, ws[R.i].w_row_bytes, K, ws[R.i].M, x, N, ldx, ws[R.i].dst, ws[R.i].ldd, reuse);
-            lane_key[R.lane] = R.key;
+            rc = mfma_mul_mat(c, ls, R.plan, ws[R.i].type, ws + R.i, R.j - R.i, K, x, N, ldx, R.plan.key == lane_key[R.lane]);
+            lane_key[R.lane] = R.plan.key;
         }
     c->ws_base = 0;
     for (int l = 1; l < nlanes; ++l) {                           // join on every path: a capture must not end with a dangling side stream

@@ -429,3 +429,197 @@ def test_switch_names_live_in_the_header_only():
             code = re.sub(r"//.*$", "", line)
             assert not re.search(r'"(?:[^"\\]|\\.)*GGML_MI355X_', code), f"{f.name}:{n}: {line.strip()[:120]}"
             assert "getenv" not in code, f"{f.name}:{n}: {line.strip()[:120]}"
+
+
+# ---- the prefill launch plan (csrc/qmm_prefill_plan.h): kernel, tile, split-K, activation prep, key and workspace of a prefill run
+
+PLAN_HEADER = ROOT / "ggml-hexagon_amd" / "csrc" / "qmm_prefill_plan.h"
+PLAN_PROBE = r"""
+#include "qmm_prefill_plan.h"
+#include <cstdlib>
+#include <iostream>
+#include <sstream>
+#include <string>
+using namespace qmm;
+static void line(const PrefillPlan & p) {
+    printf("%s%s grid=%u,%u,%u block=%u lds=%zu ksplit=%d frag=%d prep=%s perm=%d key=%d ws=%zu", p.label, p.combine_ok ? "+combine" : "", p.grid[0], p.grid[1],
+           p.grid[2], p.block, p.lds, p.ksplit, p.frag_major, p.prep_label, p.perm, p.key, p.ws_total);
+}
+int main() {
+    std::string spec;
+    while (std::getline(std::cin, spec)) {          // cus type M1,M2,.. K N n_expert flags [NAME=VAL ...]
+        std::istringstream in(spec);
+        PrefillRules r = { 256, QMM_PREC_F16_Q8, 1, 64, 128, 1, 0, 1 << 16, 1, 2, 1, 1, 1, 1 };      // qmm_ctx's defaults
+        int type, ne; unsigned flags; int64_t K, N, M[4]; std::string ms, kv;
+        in >> r.cus >> type >> ms >> K >> N >> ne >> flags;
+        int n = 0;
+        { std::istringstream m(ms); std::string x; while (std::getline(m, x, ',')) M[n++] = atoll(x.c_str()); }
+        while (in >> kv) {
+            const std::string name = kv.substr(0, kv.find('=')); const int v = atoi(kv.c_str() + kv.find('=') + 1);
+            if (name == "R64") r.r64 = v; else if (name == "SPLITK") r.splitk = v; else if (name == "SKINNY") r.skinny = v;
+            else if (name == "SKINNY_MAXN") r.skinny_max_n = r.skinny_max_n_few = v; else if (name == "WIDE") r.wide = v; else if (name == "R64S") r.r64s = v;
+            else if (name == "PREP_REG") r.prep_reg = v; else if (name == "REGB_Q23") r.regb_q23 = v; else if (name == "MM_GROUP") r.mm_group = v;
+            else if (name == "SPLITK_COMBINE") r.splitk_combine = v; else if (name == "BF16") r.prec = v ? QMM_PREC_BF16 : QMM_PREC_F16_Q8; else return 1;
+        }
+        const PrefillPlan p = prefill_plan(r, type, M, n, K, N, ne, flags);
+        if (p.per_matrix) {
+            printf("per_matrix");
+            for (int i = 0; i < n; ++i) { printf("; "); line(prefill_plan(r, type, M + i, 1, K, N, 1, flags)); }
+        } else line(p);
+        printf("\n");
+    }
+    return 0;
+}
+"""
+# (run, what the launch code did with it before the plan existed).  A run: CUs, weight type id, the rows of its 1..4 matrices, K, tokens
+# (MUL_MAT_ID: (token, slot) pairs), n_expert, flags (1 = MUL_MAT_ID, 2 = SwiGLU input, 4 = fused norm), switches off their defaults.
+# The right-hand sides were printed by the decision functions of the commit before this header (mfma_use_skinny, mfma_use_wide, mfma_splitk,
+# mfma_prep_key, launch_prep, launch_mfma, launch_mfma_regb_t, mfma_mul_mat, mfma_mul_mat_group, moe_mul_mat_id) copied into a stand-alone
+# program, never by the header: every distinct matrix of the five BASELINE workloads at 512 tokens, the few-token kernel's bounds, MoE, other
+# chip sizes, and each prefill switch off its default.  "per_matrix": the run is one launch per matrix, listed behind it.
+PLAN_TABLE = [
+    ("256 2 4096,4096,4096 4096 512 1 0",
+     "per_matrix; mfma_regb_kernel<2,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_kernel<8> perm=4 key=6 ws=37751040; mfma_regb_kernel<2,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_kernel<8> perm=4 key=6 ws=37751040; mfma_regb_kernel<2,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_kernel<8> perm=4 key=6 ws=37751040"),
+    ("256 2 4096 4096 512 1 0",
+     "mfma_regb_kernel<2,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_kernel<8> perm=4 key=6 ws=37751040"),
+    ("256 2 11008,11008 4096 512 1 0",
+     "mfma_regb_kernel<2,8,128> grid=86,4,1 block=512 lds=32768 ksplit=1 frag=0 prep=prep_act_kernel<8> perm=4 key=6 ws=4196608"),
+    ("256 2 4096 11008 512 1 2",
+     "mfma_regb_kernel<2,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_kernel<8> perm=4 key=6 ws=44828928"),
+    ("256 14 32000 4096 512 1 0",
+     "mfma_regb_kernel<14,8,128> grid=125,4,1 block=512 lds=65536 ksplit=1 frag=0 prep=prep_act_q8k_kernel<3> perm=3 key=26 ws=4196608"),
+    ("256 12 4096,1024,1024 4096 512 1 0",
+     "mfma_regb_kernel<12,8,128> grid=24,4,2 block=512 lds=32768 ksplit=2 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=29362432"),
+    ("256 12 4096,1024 4096 512 1 0",
+     "mfma_regb_kernel<12,8,128> grid=20,4,3 block=512 lds=32768 ksplit=3 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=35653888"),
+    ("256 14 1024 4096 512 1 0",
+     "mfma_regb_kernel<14,8,128> grid=4,4,8 block=512 lds=65536 ksplit=8 frag=0 prep=prep_act_q8k_kernel<3> perm=3 key=26 ws=20973824"),
+    ("256 12 4096 4096 512 1 0",
+     "mfma_regb_kernel<12,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=37751040"),
+    ("256 12 14336,14336 4096 512 1 0",
+     "mfma_r64s_q4k_kernel<2> grid=112,2,1 block=256 lds=0 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=4196608"),
+    ("256 12 4096 14336 512 1 2",
+     "mfma_regb_kernel<12,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=48236800"),
+    ("256 14 4096 14336 512 1 2",
+     "mfma_regb_kernel<14,8,128> grid=16,4,4 block=512 lds=65536 ksplit=4 frag=0 prep=prep_act_q8k_kernel<3> perm=3 key=26 ws=48236800"),
+    ("256 14 128256 4096 512 1 0",
+     "mfma_regb_kernel<14,8,128> grid=501,4,1 block=512 lds=65536 ksplit=1 frag=0 prep=prep_act_q8k_kernel<3> perm=3 key=26 ws=4196608"),
+    ("256 12 8192,1024 8192 512 1 0",
+     "per_matrix; mfma_regb_kernel<12,8,128> grid=32,4,2 block=512 lds=32768 ksplit=2 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=41945344; mfma_regb_kernel<12,8,128> grid=4,4,8 block=512 lds=32768 ksplit=8 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=25168128"),
+    ("256 13 1024 8192 512 1 0",
+     "mfma_regb_kernel<13,8,128> grid=4,4,8 block=512 lds=32768 ksplit=8 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=25168128"),
+    ("256 14 1024 8192 512 1 0",
+     "mfma_regb_kernel<14,8,128> grid=4,4,8 block=512 lds=65536 ksplit=8 frag=0 prep=prep_act_q8k_kernel<3> perm=3 key=26 ws=25168128"),
+    ("256 12 8192 8192 512 1 0",
+     "mfma_regb_kernel<12,8,128> grid=32,4,2 block=512 lds=32768 ksplit=2 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=41945344"),
+    ("256 12 28672,28672 8192 512 1 0",
+     "mfma_r64s_q4k_kernel<2> grid=224,2,1 block=256 lds=0 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=8390912"),
+    ("256 12 8192 28672 512 1 2",
+     "mfma_regb_kernel<12,8,128> grid=32,4,2 block=512 lds=32768 ksplit=2 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=62916864"),
+    ("256 14 8192 28672 512 1 2",
+     "mfma_regb_kernel<14,8,128> grid=32,4,2 block=512 lds=65536 ksplit=2 frag=0 prep=prep_act_q8k_kernel<3> perm=3 key=26 ws=62916864"),
+    ("256 14 128256 8192 512 1 0",
+     "mfma_regb_kernel<14,8,128> grid=501,4,1 block=512 lds=65536 ksplit=1 frag=0 prep=prep_act_q8k_kernel<3> perm=3 key=26 ws=8390912"),
+    ("256 12 4096 4096 512 1 0",
+     "mfma_regb_kernel<12,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=37751040"),
+    ("256 8 1024,1024 4096 512 1 0",
+     "mfma_regb_kernel<8,8,128> grid=8,4,8 block=512 lds=32768 ksplit=8 frag=0 prep=prep_act_kernel<8> perm=5 key=18 ws=37751040"),
+    ("256 13 4096 4096 512 1 0",
+     "mfma_regb_kernel<13,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=37751040"),
+    ("256 12 14336 4096 1024 8 1",
+     "mfma_regb_kernel<12,8,128> grid=56,8,8 block=512 lds=32768 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=0 ws=9458944"),
+    ("256 12 4096 14336 1024 8 1",
+     "mfma_regb_kernel<12,8,128> grid=16,8,8 block=512 lds=32768 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=0 ws=33051904"),
+    ("256 14 4096 14336 1024 8 1",
+     "mfma_regb_kernel<14,8,128> grid=16,8,8 block=512 lds=65536 ksplit=1 frag=0 prep=prep_act_q8k_kernel<3> perm=3 key=0 ws=33051904"),
+    ("256 14 32000 4096 512 1 0",
+     "mfma_regb_kernel<14,8,128> grid=125,4,1 block=512 lds=65536 ksplit=1 frag=0 prep=prep_act_q8k_kernel<3> perm=3 key=26 ws=4196608"),
+    ("256 12 4096,4096,4096 4096 512 1 0",
+     "per_matrix; mfma_regb_kernel<12,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=37751040; mfma_regb_kernel<12,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=37751040; mfma_regb_kernel<12,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=37751040"),
+    ("256 12 11008,11008 4096 512 1 0",
+     "mfma_regb_kernel<12,8,128> grid=86,4,1 block=512 lds=32768 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=4196608"),
+    ("256 12 4096 11008 512 1 2",
+     "mfma_regb_kernel<12,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_kernel<15> perm=2 key=26 ws=44828928"),
+    ("256 12 32000 4096 512 1 0",
+     "mfma_r64s_q4k_kernel<2> grid=125,2,1 block=256 lds=0 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=4196608"),
+    ("256 12 4096 4096 64 1 0",
+     "mfma_skinny_kernel<12,8,2> grid=128,1,1 block=512 lds=0 ksplit=1 frag=1 prep=prep_act_q8k_kernel<2> perm=2 key=27 ws=1049344"),
+    ("256 12 4096 4096 65 1 0",
+     "mfma_skinny_kernel<12,8,2> grid=128,2,1 block=512 lds=0 ksplit=1 frag=1 prep=prep_act_q8k_kernel<2> perm=2 key=27 ws=1049344"),
+    ("256 12 14336 4096 65 1 0",
+     "mfma_regb_kernel<12,8,128> grid=56,1,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=15958784"),
+    ("256 12 4096 4096 128 1 0",
+     "mfma_skinny_kernel<12,8,2> grid=128,2,1 block=512 lds=0 ksplit=1 frag=1 prep=prep_act_q8k_kernel<2> perm=2 key=27 ws=1049344"),
+    ("256 12 4096 4096 129 1 0",
+     "mfma_regb_kernel<12,8,128> grid=16,2,8 block=512 lds=32768 ksplit=8 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=19006720"),
+    ("256 12 4096,1024,1024 4096 128 1 0",
+     "per_matrix; mfma_skinny_kernel<12,8,2> grid=128,2,1 block=512 lds=0 ksplit=1 frag=1 prep=prep_act_q8k_kernel<2> perm=2 key=27 ws=1049344; mfma_skinny_kernel<12,8,2> grid=32,2,1 block=512 lds=0 ksplit=1 frag=1 prep=prep_act_q8k_kernel<2> perm=2 key=27 ws=1049344; mfma_skinny_kernel<12,8,2> grid=32,2,1 block=512 lds=0 ksplit=1 frag=1 prep=prep_act_q8k_kernel<2> perm=2 key=27 ws=1049344"),
+    ("256 12 4096,1024,1024 4096 512 1 4",
+     "mfma_regb_kernel<12,8,128> grid=24,4,2 block=512 lds=32768 ksplit=2 frag=0 prep=prep_act_q8k_kernel<2,norm> perm=2 key=26 ws=29362432"),
+    ("256 12 14336 4096 64 8 1",
+     "mfma_skinny_kernel<12,8,2> grid=448,1,8 block=512 lds=0 ksplit=1 frag=1 prep=prep_act_q8k_kernel<2> perm=2 key=0 ws=1575424"),
+    ("304 12 4096,1024,1024 4096 512 1 0",
+     "mfma_regb_kernel<12,8,128> grid=24,4,3 block=512 lds=32768 ksplit=3 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=41945344"),
+    ("64 12 14336,14336 4096 512 1 0",
+     "mfma_r64s_q4k_kernel<2> grid=112,2,1 block=256 lds=0 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=4196608"),
+    ("256 12 14336,14336 4096 512 1 0 R64=0",
+     "mfma_regb_q4k_wide_kernel<8> grid=112,2,1 block=512 lds=65536 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=4196608"),
+    ("256 12 4096 4096 512 1 0 R64=1",
+     "mfma_r64_q4k_kernel<4> grid=16,4,4 block=256 lds=0 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=37751040"),
+    ("256 12 14336,14336 4096 512 1 0 R64=3",
+     "mfma_r64s_q4k_kernel<2> grid=112,2,1 block=256 lds=0 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=4196608"),
+    ("256 12 14336,14336 4096 512 1 0 R64S=0",
+     "mfma_r64_q4k_kernel<8> grid=112,2,1 block=256 lds=0 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=4196608"),
+    ("256 12 14336,14336 4096 512 1 0 WIDE=0",
+     "mfma_regb_kernel<12,8,128> grid=112,4,1 block=512 lds=32768 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=4196608"),
+    ("256 12 4096 4096 512 1 0 SPLITK=0",
+     "mfma_regb_kernel<12,4,64> grid=32,8,1 block=256 lds=16384 ksplit=1 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=4196608"),
+    ("256 12 4096,1024,1024 4096 512 1 0 SPLITK=2",
+     "mfma_regb_kernel<12,8,128> grid=24,4,2 block=512 lds=32768 ksplit=2 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=29362432"),
+    ("256 12 4096 4096 512 1 0 SPLITK_COMBINE=1",
+     "mfma_regb_kernel<12,8,128>+combine grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=37751040"),
+    ("256 12 4096 4096 32 1 0 SKINNY=0",
+     "mfma_regb_kernel<12,8,128> grid=16,1,8 block=512 lds=32768 ksplit=8 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=5243648"),
+    ("256 12 4096 4096 96 1 0 SKINNY_MAXN=96",
+     "mfma_skinny_kernel<12,8,2> grid=128,2,1 block=512 lds=0 ksplit=1 frag=1 prep=prep_act_q8k_kernel<2> perm=2 key=27 ws=1049344"),
+    ("256 12 4096,1024,1024 4096 512 1 0 MM_GROUP=0",
+     "per_matrix; mfma_regb_kernel<12,8,128> grid=16,4,4 block=512 lds=32768 ksplit=4 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=37751040; mfma_regb_kernel<12,8,128> grid=4,4,8 block=512 lds=32768 ksplit=8 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=20973824; mfma_regb_kernel<12,8,128> grid=4,4,8 block=512 lds=32768 ksplit=8 frag=0 prep=prep_act_q8k_kernel<2> perm=2 key=26 ws=20973824"),
+    ("256 14 4096 14336 512 1 0 PREP_REG=0",
+     "mfma_regb_kernel<14,8,128> grid=16,4,4 block=512 lds=65536 ksplit=4 frag=0 prep=prep_act_kernel<15> perm=3 key=26 ws=48236800"),
+    ("256 11 4096,1024 4096 512 1 0 REGB_Q23=0",
+     "per_matrix; mfma_kernel<11,64> grid=64,4,1 block=512 lds=98304 ksplit=1 frag=0 prep=prep_act_q8k_kernel<0> perm=0 key=24 ws=4196608; mfma_kernel<11,64> grid=16,4,1 block=512 lds=98304 ksplit=1 frag=0 prep=prep_act_q8k_kernel<0> perm=0 key=24 ws=4196608"),
+    ("256 14 4096 4096 512 1 0 BF16=1",
+     "mfma_kernel<14,64> grid=64,4,1 block=512 lds=98304 ksplit=1 frag=0 prep=prep_act_kernel<15> perm=0 key=0 ws=4196608"),
+]
+
+
+@pytest.fixture(scope="module")
+def plan_probe(tmp_path_factory):
+    """the plan header alone, compiled by the host compiler (no HIP, no ggml) into a program that prints the plan of each run on its input"""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    d = tmp_path_factory.mktemp("plan")
+    (d / "probe.cpp").write_text(PLAN_PROBE)
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", f"-I{PLAN_HEADER.parent}", str(d / "probe.cpp"), "-o", str(d / "probe")], check=True)
+    return lambda specs: subprocess.run([str(d / "probe")], input="\n".join(specs) + "\n", check=True, capture_output=True, text=True).stdout.splitlines()
+
+
+def test_prefill_plan_keeps_every_decision(plan_probe):
+    assert len(PLAN_TABLE) >= 40
+    got = plan_probe([spec for spec, _ in PLAN_TABLE])
+    assert len(got) == len(PLAN_TABLE)
+    for (spec, want), line in zip(PLAN_TABLE, got):
+        assert line == want, spec
+
+
+def test_prefill_rules_live_in_the_plan_header_only():
+    """the decision functions are the plan's own: no other file in csrc/ calls or defines them (comments may speak of them)"""
+    for f in sorted((ROOT / "ggml-hexagon_amd" / "csrc").iterdir()):
+        if f == PLAN_HEADER or f.suffix not in (".cpp", ".h", ".hip", ".hiph"):
+            continue
+        for n, line in enumerate(f.read_text().splitlines(), 1):
+            code = re.sub(r"//.*$", "", line)
+            assert not re.search(r"\b(mfma_use_skinny|mfma_use_wide|mfma_splitk)\b", code), f"{f.name}:{n}: {line.strip()[:120]}"
