@@ -62,7 +62,7 @@ def build_plugin(force: bool = False) -> Path | None:
     src = CSRC / "ggml-mi355x.cpp"              # one translation unit: it includes the other sections (mi355x_*.cpp, one per concern)
     if not src.exists():
         return None
-    srcs = [src] + sorted(CSRC.glob("mi355x_*")) + [CSRC / "qmm_switches.h",
+    srcs = [src] + sorted(CSRC.glob("mi355x_*")) + [CSRC / "qmm_switches.h", CSRC / "qmm_matvec_plan.h", CSRC / "qmm_types.h",
                     ROOT / "include" / "ggml-mi355x.h", ROOT / "include" / "ggml_mi355x_qmm.h", ROOT / "include" / "ggml_mi355x_ops.h"]
     if not force and _newer(PLUGIN_SO, srcs + [QMM_SO]):
         return PLUGIN_SO

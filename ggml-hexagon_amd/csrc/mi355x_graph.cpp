@@ -255,7 +255,7 @@ enum ggml_status compute_mul_mat(mi355x_backend_ctx * ctx, ggml_tensor * const *
         }
         // (c) ffn_gate + ffn_up of a few-token batch whose only readers are silu(gate) and the MUL of the two (build_ffn's SwiGLU):
         //     the kernel pairs the rows and writes the product; neither projection is stored
-        if (n == 2 && N <= QMM_MATVEC_MAX_N && ws[0].type == ws[1].type && ws[0].M == ws[1].M && !fuse_off()) {
+        if (n == 2 && N <= QMM_MATVEC_MAX_N && qmm::mv_swiglu_pair(ws[0].type, ws[0].M, ws[1].type, ws[1].M) && !fuse_off()) {
             auto uses = [&](const ggml_tensor * t) {
                 auto it = std::lower_bound(ctx->readers.begin(), ctx->readers.end(), t,
                                            [](const mi355x_backend_ctx::reader_info & r, const ggml_tensor * y) { return r.t < y; });
@@ -286,7 +286,7 @@ enum ggml_status compute_mul_mat(mi355x_backend_ctx * ctx, ggml_tensor * const *
             if (jm >= 0 && !early_ok && dbg()) fprintf(stderr, "fusion declined: SwiGLU into %s\n", nodes[jm]->name);
             if (jm >= 0 && early_ok && uses(t0) == 1 && uses(t1) == 1 && uses(nodes[js]) == 1 && ggml_are_same_shape(nodes[jm], t0) && nodes[jm]->nb[0] == 4 &&
                 !(nodes[jm]->flags & GGML_TENSOR_FLAG_OUTPUT) && !(t0->flags & GGML_TENSOR_FLAG_OUTPUT) && !(t1->flags & GGML_TENSOR_FLAG_OUTPUT) &&
-                (size_t) N * K * 5 / 4 + (ex.norm_w ? (size_t) N * K * 4 : 0) + 4096 <= 150 * 1024) {
+                qmm::mv_fits_swiglu(N, K, ex.norm_w != nullptr)) {
                 ex.swiglu = nodes[js]->src[0] == t0 ? 1 : 2;
                 ws[0].dst = (float *) nodes[jm]->data;
                 ws[0].ldd = (int64_t) (nodes[jm]->nb[1] / sizeof(float));
@@ -1092,7 +1092,7 @@ int graph_pass::site_rms_norm_mul(int i, ggml_tensor * node, int gop) {
         const int64_t K = node->ne[0], N = node->ne[1];
         if (g.all && !(mul->flags & GGML_TENSOR_FLAG_OUTPUT) && x->nb[0] == 4 && x->nb[1] % 16 == 0 &&
             (uintptr_t) to_qt(x, ctx).data % 16 == 0 && (uintptr_t) other->data % 16 == 0 && K % 256 == 0 &&
-            (size_t) N * K * 4 + (size_t) N * K * 11 / 8 + 4096 <= 150 * 1024) {
+            qmm::mv_fits_norm(N, K)) {
             ctx->pending_norm = { node, mul, other, g.n };
             done[i + 1] = 1;
             return 1;

@@ -14,6 +14,7 @@
 #include "ggml_mi355x_qmm.h"
 #include "ggml_mi355x_ops.h"
 #include "qmm_switches.h"
+#include "qmm_matvec_plan.h"
 
 #include <algorithm>
 #include <array>

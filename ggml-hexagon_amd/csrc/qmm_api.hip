@@ -14,14 +14,6 @@
 
 using namespace qmm;
 
-namespace {
-
-bool type_ok(int t) { return type_known(t); }
-int  blck(int t) { return type_blck(t); }
-int  tsize(int t) { return type_tsize(t); }
-
-} // namespace
-
 template <int T>
 static int launch_dequant(hipStream_t st, const void * w, int64_t rb, int64_t rows, int64_t K, float * dst) {
     const int64_t n = rows * (K / Traits<T>::UNIT_W);
@@ -32,91 +24,58 @@ static int launch_dequant(hipStream_t st, const void * w, int64_t rb, int64_t ro
     return QMM_OK;
 }
 
-static bool group_has_extras(const MatvecGroup & g) {
-    bool ex = g.norm_w != nullptr || g.swiglu != 0;
-    for (int i = 0; i < g.n; ++i) ex = ex || g.res[i] != nullptr;
-    return ex;
-}
+static_assert(QMM_MATVEC_MAX_N == 8, "QMM_FOR_NTOK lists the token counts");
 
-template <int T, int NTOK>
-static int launch_matvec_n(qmm_ctx * c, hipStream_t st, const MatvecGroup & g, const float * x, int64_t ldx, int K) {
-    const size_t lds = matvec_lds_bytes<T, NTOK>(K) + (g.norm_w ? (size_t) NTOK * K * 4 : 0);
-    if (lds > 160 * 1024) return fail(QMM_EUNSUPPORTED, "matvec: %d tokens x K=%d needs %zu B of LDS", NTOK, K, lds);
-    auto kern = group_has_extras(g) ? matvec_kernel<T, NTOK, true> : matvec_kernel<T, NTOK, false>;
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    const int total = g.swiglu ? g.row_end[0] : g.row_end[g.n - 1];
-    // one block per CU (the activation vector is quantized once per CU); 16 waves per block unless there are
-    // fewer rows than that per CU.  Every wave gets a contiguous chunk of rows (+-1 row balance).
-    int nw = (total + c->cus - 1) / c->cus;
-    nw = nw >= 16 ? 16 : nw > 8 ? 16 : nw > 4 ? 8 : 4;
-    int blocks = (total + nw - 1) / nw;
-    if (blocks > c->cus * c->mv_bpc) blocks = c->cus * c->mv_bpc;
-    QMM_TRACE(c, "matvec_kernel<%d,%d,%s>", T, NTOK, group_has_extras(g) ? "true" : "false");
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nw * WAVE), lds, st, g, x, ldx, K, c->act_mode | (c->mv_onepass ? 0 : 256), g.row_end[g.n - 1]);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
+static MatvecRules matvec_rules(const qmm_ctx * c) { return { c->cus, c->mv_bpc, c->mv_kmix, c->mv_onepass, c->act_mode }; }
 
-// (q80: the group holds Q8_0 matrices too; no fused norm, N <= 4: mul_mat_group_impl)
-template <int NTOK>
-static int launch_kmix_n(qmm_ctx * c, hipStream_t st, const MatvecGroup & g, const float * x, int64_t ldx, int K, bool q80 = false) {
-    const size_t lds = kmix_lds_bytes(NTOK, K) + (g.norm_w ? (size_t) NTOK * K * 4 : 0) + (q80 ? matvec_lds_bytes<T_Q8_0P, NTOK>(K) : 0);
-    if (lds > 160 * 1024) return fail(QMM_EUNSUPPORTED, "mixed-type matvec: %d tokens x K=%d needs %zu B of LDS", NTOK, K, lds);
-    auto kern = group_has_extras(g) ? matvec_kmix_kernel<NTOK, true> : matvec_kmix_kernel<NTOK, false>;
-    if constexpr (NTOK <= 4) {
-        if (q80) kern = group_has_extras(g) ? matvec_kmix_kernel<NTOK, true, true> : matvec_kmix_kernel<NTOK, false, true>;
-    } else if (q80) {
-        return fail(QMM_EUNSUPPORTED, "mixed-format matvec: up to 4 tokens");
+using MatvecKernel = void (*)(MatvecGroup, const float *, int64_t, int, int, int);
+
+// the plan's instantiation for NT tokens (with Q8_0 matrices in a mixed group the kernel exists for NT <= 4 only, no fused norm: matvec_group_plan)
+template <int NT> static MatvecKernel matvec_instance(const MatvecLaunch & l) {
+    if constexpr (NT <= 4) {
+        if (l.kind == MV_MIXED_Q80) return l.ex ? matvec_kmix_kernel<NT, true, true> : matvec_kmix_kernel<NT, false, true>;
     }
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    const int total = g.row_end[g.n - 1];
-    int nw = (total + c->cus - 1) / c->cus;
-    nw = nw > 8 ? 16 : nw > 4 ? 8 : 4;
-    int blocks = (total + nw - 1) / nw;
-    if (blocks > c->cus * c->mv_bpc) blocks = c->cus * c->mv_bpc;
-    QMM_TRACE(c, q80 ? "matvec_kmix_kernel<%d,%s,q8_0>" : "matvec_kmix_kernel<%d,%s>", NTOK, group_has_extras(g) ? "true" : "false");
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nw * WAVE), lds, st, g, x, ldx, K, c->act_mode | (c->mv_onepass ? 0 : 256), total);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
-static int launch_kmix(qmm_ctx * c, hipStream_t st, const MatvecGroup & g, const float * x, int64_t ldx, int K, int N, bool q80 = false) {
-    switch (N) {
-        case 1: return launch_kmix_n<1>(c, st, g, x, ldx, K, q80);
-        case 2: return launch_kmix_n<2>(c, st, g, x, ldx, K, q80);
-        case 3: return launch_kmix_n<3>(c, st, g, x, ldx, K, q80);
-        case 4: return launch_kmix_n<4>(c, st, g, x, ldx, K, q80);
-        case 5: return launch_kmix_n<5>(c, st, g, x, ldx, K, q80);
-        case 6: return launch_kmix_n<6>(c, st, g, x, ldx, K, q80);
-        case 7: return launch_kmix_n<7>(c, st, g, x, ldx, K, q80);
-        case 8: return launch_kmix_n<8>(c, st, g, x, ldx, K, q80);
-        default: return fail(QMM_EINVAL, "kmix matvec: N=%d", N);
-    }
-}
-
-template <int T>
-static int launch_matvec(qmm_ctx * c, hipStream_t st, const MatvecGroup & g, const float * x, int64_t ldx, int K, int N) {
-    switch (N) {
-        case 1: return launch_matvec_n<T, 1>(c, st, g, x, ldx, K);
-        case 2: return launch_matvec_n<T, 2>(c, st, g, x, ldx, K);
-        case 3: return launch_matvec_n<T, 3>(c, st, g, x, ldx, K);
-        case 4: return launch_matvec_n<T, 4>(c, st, g, x, ldx, K);
-        case 5: return launch_matvec_n<T, 5>(c, st, g, x, ldx, K);
-        case 6: return launch_matvec_n<T, 6>(c, st, g, x, ldx, K);
-        case 7: return launch_matvec_n<T, 7>(c, st, g, x, ldx, K);
-        case 8: return launch_matvec_n<T, 8>(c, st, g, x, ldx, K);
-        default: return fail(QMM_EINVAL, "matvec: N=%d", N);
-    }
-}
-
-static int matvec_any(qmm_ctx * c, hipStream_t st, int type, const MatvecGroup & g, const float * x, int64_t ldx, int K, int N) {
-#define QMM_X(TT) return launch_matvec<TT>(c, st, g, x, ldx, K, N)
-    QMM_FOR_TYPE(type, QMM_X)
+    if (l.kind != MV_PER_TYPE) return l.ex ? matvec_kmix_kernel<NT, true> : matvec_kmix_kernel<NT, false>;
+#define QMM_X(TT) return l.ex ? matvec_kernel<TT, NT, true> : matvec_kernel<TT, NT, false>
+    QMM_FOR_TYPE(l.type, QMM_X)
 #undef QMM_X
 }
 
+// the executor of every few-token launch (group calls and chain steps that go out on their own): the plan's instantiation on g
+static int run_matvec(qmm_ctx * c, hipStream_t st, const MatvecLaunch & l, const MatvecGroup & g, const float * x, int64_t ldx) {
+    char text[96];
+    if (l.error) { l.text(text, sizeof(text)); return fail(l.error, "%s", text); }
+    MatvecKernel kern = nullptr;
+#define QMM_X(NT) kern = matvec_instance<NT>(l); break
+    QMM_FOR_NTOK(l.ntok, QMM_X)
+#undef QMM_X
+    if (!kern) return fail(QMM_EINVAL, l.kind == MV_PER_TYPE ? "matvec: N=%d" : "kmix matvec: N=%d", l.ntok);
+    if (l.lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) l.lds));
+    if (c->trace) { l.text(text, sizeof(text)); QMM_TRACE(c, "%s", text); }
+    hipLaunchKernelGGL(kern, dim3(l.blocks), dim3(l.waves * WAVE), l.lds, st, g, x, ldx, l.K, l.act_arg, g.row_end[g.n - 1]);
+    HIP_TRY(hipGetLastError());
+    return QMM_OK;
+}
+
+// matrices idx[0 .. n - 1] of a call (cumulative rows row_end) from token n0 on, with what the caller folds in, as the kernels' argument
+static MatvecGroup matvec_group(const qmm_weight * ws, const int * idx, const int * row_end, int n, int64_t n0, const qmm_mv_extra * ex) {
+    MatvecGroup g;
+    memset(&g, 0, sizeof(g));
+    for (int m = 0; m < n; ++m) {
+        const qmm_weight & w = ws[idx[m]];
+        g.w[m] = (const uint8_t *) w.w;  g.dst[m] = w.dst + n0 * w.ldd;  g.row_bytes[m] = w.w_row_bytes;  g.ldd[m] = w.ldd;
+        g.type[m] = w.type;
+        g.row_end[m] = row_end[m];
+        if (ex && ex->residual[idx[m]]) g.res[m] = ex->residual[idx[m]] + n0 * w.ldd;
+    }
+    g.n = n;
+    if (ex) { g.norm_w = ex->norm_w; g.norm_eps = ex->norm_eps; g.swiglu = ex->swiglu; }
+    return g;
+}
+
 static int check_mm(int type, const void * w, int64_t rb, int64_t K, const float * x, int64_t ldx, const char * who) {
-    if (!type_ok(type)) return fail(QMM_EUNSUPPORTED, "%s: type %d not supported", who, type);
-    if (K <= 0 || K % blck(type)) return fail(QMM_EUNSUPPORTED, "%s: K=%lld must be a multiple of %d", who, (long long) K, blck(type));
+    if (!type_known(type)) return fail(QMM_EUNSUPPORTED, "%s: type %d not supported", who, type);
+    if (K <= 0 || K % type_blck(type)) return fail(QMM_EUNSUPPORTED, "%s: K=%lld must be a multiple of %d", who, (long long) K, type_blck(type));
     if (rb < (int64_t) qmm_row_size(type, K)) return fail(QMM_EINVAL, "%s: weight row stride %lld < row size", who, (long long) rb);
     if ((uintptr_t) x % 16 || ldx % 4 || ldx < K) return fail(QMM_EINVAL, "%s: src1 must be 16-byte aligned with ldx %% 4 == 0", who);
     if (type_planar(type) && (!qmm_planar_type(type_base(type), K, rb) || (uintptr_t) w % 16))
@@ -127,9 +86,6 @@ static int check_mm(int type, const void * w, int64_t rb, int64_t K, const float
 
 // ------------------------------------------------------------------------------------------- chains (qmm_chain.hiph)
 
-static size_t chain_act_bytes(int fam, int ntok, int K) {
-    return fam == CHAIN_FAM_Q8_K ? kmix_lds_bytes(ntok, K) : (((size_t) ntok * K + (size_t) ntok * (K / 32) * 4 + 15) & ~(size_t) 15);
-}
 static size_t chain_step_lds(const ChainStep & st, int ntok) {
     return chain_act_bytes(st.fam, ntok, st.K) + (st.g.norm_w ? (size_t) ntok * st.K * 4 : 0);
 }
@@ -137,10 +93,8 @@ constexpr size_t CHAIN_SLAB = (size_t) CHAIN_RPW * CHAIN_NW * 4;          // one
 
 // the step as a launch of its own (a chain of one, or chains switched off): the kernels of round 1
 static int chain_step_plain(qmm_ctx * c, hipStream_t st, const ChainStep & s) {
-    bool uniform = true;
-    for (int i = 1; i < s.g.n; ++i) uniform = uniform && s.g.type[i] == s.g.type[0];
-    if (uniform) return matvec_any(c, st, s.g.type[0], s.g, s.x, s.ldx, s.K, 1);
-    return launch_kmix(c, st, s.g, s.x, s.ldx, s.K, 1);
+    const MatvecLaunch l = matvec_launch(matvec_rules(c), mv_kind_of(s.g.type, s.g.n), s.g.type[0], nullptr, s.g.row_end, s.g.n, s.K, 0, 1, s.g.norm_w != nullptr, s.g.swiglu, s.g.res);
+    return run_matvec(c, st, l, s.g, s.x, s.ldx);
 }
 
 static int chain_launch(qmm_ctx * c) {
@@ -174,7 +128,7 @@ static int chain_launch(qmm_ctx * c) {
             const size_t total = a.res_off + CHAIN_SLAB;
             auto kern = matvec_chain_kernel<1>;
             if (!c->chain_attr_set) {
-                hipError_t e = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+                hipError_t e = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) MV_LDS_LAUNCH - 256);
                 if (e != hipSuccess) { rc = fail(QMM_EHIP, "chain: hipFuncSetAttribute: %s", hipGetErrorString(e)); break; }
                 c->chain_attr_set = true;
             }
@@ -200,9 +154,8 @@ static int chain_record(qmm_ctx * c, hipStream_t st, const qmm_weight * ws, int 
     int64_t rows = 0;
     for (int i = 0; i < nw; ++i) {
         if (ws[i].M <= 0) return 0;
-        if (ws[i].type != T_Q4_0 && ws[i].type != T_Q8_0 && ws[i].type != T_Q4_K && ws[i].type != T_Q5_K && ws[i].type != T_Q6_K) return 0;
-        const bool kq = ws[i].type == T_Q4_K || ws[i].type == T_Q5_K || ws[i].type == T_Q6_K;
-        fams[kq ? 1 : 0]++;
+        if (chain_family(ws[i].type) == CHAIN_FAM_NONE) return 0;
+        fams[chain_family(ws[i].type)]++;
         rows += ws[i].M;
         // a result on top of the activations is a race between workgroups in any launch form: leave it to the caller's order
         const char * d0 = (const char *) ws[i].dst, * x0 = (const char *) x;
@@ -211,7 +164,7 @@ static int chain_record(qmm_ctx * c, hipStream_t st, const qmm_weight * ws, int 
     if (fams[1] && K % 256) return 0;
     if ((rows + W - 1) / W > CHAIN_RPW) return 0;
     if (ex && ex->swiglu && fams[0] && fams[1]) return 0;
-    if (chain_act_bytes(fams[1] ? CHAIN_FAM_Q8_K : CHAIN_FAM_Q8_0, 1, (int) K) + (ex && ex->norm_w ? (size_t) K * 4 : 0) + CHAIN_SLAB + 1024 > 150 * 1024) return 0;
+    if (!chain_step_fits(fams[1] ? CHAIN_FAM_Q8_K : CHAIN_FAM_Q8_0, K, ex && ex->norm_w, CHAIN_SLAB)) return 0;
     if (c->chain->empty()) c->chain_stream = st;
     else if (c->chain_stream != st) { int rc = chain_launch(c); if (rc) return rc; c->chain_stream = st; }
     bool first = true;
@@ -219,18 +172,10 @@ static int chain_record(qmm_ctx * c, hipStream_t st, const qmm_weight * ws, int 
         if (!fams[fam]) continue;
         ChainStep s;
         memset(&s, 0, sizeof(s));
-        int r = 0;
-        for (int i = 0; i < nw; ++i) {
-            const bool kq = ws[i].type == T_Q4_K || ws[i].type == T_Q5_K || ws[i].type == T_Q6_K;
-            if ((kq ? 1 : 0) != fam) continue;
-            const int k = s.g.n++;
-            s.g.w[k] = (const uint8_t *) ws[i].w;  s.g.dst[k] = ws[i].dst;  s.g.row_bytes[k] = ws[i].w_row_bytes;  s.g.ldd[k] = ws[i].ldd;
-            s.g.type[k] = ws[i].type;
-            r += (int) ws[i].M;
-            s.g.row_end[k] = r;
-            s.g.res[k] = ex ? ex->residual[i] : nullptr;
-        }
-        if (ex) { s.g.norm_w = ex->norm_w; s.g.norm_eps = ex->norm_eps; s.g.swiglu = ex->swiglu; }
+        int n = 0, r = 0, idx[MV_MAX_GROUP], row_end[MV_MAX_GROUP];
+        for (int i = 0; i < nw; ++i)
+            if (chain_family(ws[i].type) == fam) { idx[n] = i; row_end[n++] = r += (int) ws[i].M; }
+        s.g = matvec_group(ws, idx, row_end, n, 0, ex);
         s.x = x;  s.ldx = ldx;  s.K = (int) K;  s.fam = fam;
         s.dep = first ? 1 : 0;                          // the second format of one call reads the same x and writes other rows
         s.restage = 1;
@@ -540,15 +485,15 @@ int qmm_synchronize(qmm_ctx * c, void * st) {
 }
 
 size_t qmm_row_size(int type, int64_t k) {
-    if (!type_ok(type) || k % blck(type)) return 0;
-    return (size_t) (k / blck(type)) * tsize(type);
+    if (!type_known(type) || k % type_blck(type)) return 0;
+    return (size_t) (k / type_blck(type)) * type_tsize(type);
 }
 
 // ------------------------------------------------------------------------------------------- dequantize
 
 int qmm_dequantize(qmm_ctx * c, int type, const void * w, int64_t rb, int64_t rows, int64_t K, float * dst, void * st) {
-    if (!c || !type_ok(type)) return fail(QMM_EINVAL, "qmm_dequantize: bad ctx/type %d", type);
-    if (K <= 0 || K % blck(type)) return fail(QMM_EINVAL, "qmm_dequantize: K=%lld", (long long) K);
+    if (!c || !type_known(type)) return fail(QMM_EINVAL, "qmm_dequantize: bad ctx/type %d", type);
+    if (K <= 0 || K % type_blck(type)) return fail(QMM_EINVAL, "qmm_dequantize: K=%lld", (long long) K);
     if (rb < (int64_t) qmm_row_size(type, K)) return fail(QMM_EINVAL, "qmm_dequantize: row stride too small");
     if ((uintptr_t) dst % 16) return fail(QMM_EINVAL, "qmm_dequantize: dst must be 16-byte aligned");
     HIP_TRY(hipSetDevice(c->device));
@@ -575,7 +520,7 @@ int qmm_repack_rows(qmm_ctx * c, int type, void * w, int64_t w_row_bytes, int64_
     HIP_TRY(hipSetDevice(c->device));
     QMM_CHAIN_FLUSH(c);
     const size_t lds = qmm_row_size(type, K);
-    if (lds > 150 * 1024) return fail(QMM_EUNSUPPORTED, "qmm_repack_rows: a row of %zu bytes does not fit LDS", lds);
+    if (lds > MV_LDS_FIT) return fail(QMM_EUNSUPPORTED, "qmm_repack_rows: a row of %zu bytes does not fit LDS", lds);
 #define QMM_RP(TT, DIR)                                                                                                             \
     do {                                                                                                                            \
         auto kern = repack_rows_kernel<TT, DIR>;                                                                                    \
@@ -619,24 +564,11 @@ static int mul_mat_group_impl(qmm_ctx * c, const qmm_weight * ws, int nw, int64_
                               const qmm_mv_extra * ex) {
     if (!c || !ws || nw <= 0) return fail(QMM_EINVAL, "qmm_mul_mat_group: bad arguments");
     if (N <= 0) return QMM_OK;
-    const float * norm_w = ex ? ex->norm_w : nullptr;
-    if (ex) {
-        if (N > QMM_MATVEC_MAX_N || nw > MV_MAX_GROUP) return fail(QMM_EUNSUPPORTED, "qmm_mul_mat_group_ex: batches of <= %d tokens, <= %d matrices", QMM_MATVEC_MAX_N, MV_MAX_GROUP);
-        if (norm_w && ((uintptr_t) norm_w % 16 || ex->norm_eps < 0.0f)) return fail(QMM_EINVAL, "qmm_mul_mat_group_ex: norm weight must be 16-byte aligned, eps >= 0");
-        if (norm_w && (size_t) N * K * 4 + (size_t) N * K * 11 / 8 + 4096 > 150 * 1024) return fail(QMM_EUNSUPPORTED, "qmm_mul_mat_group_ex: %lld rows of %lld do not fit LDS with the norm", (long long) N, (long long) K);
-        if (ex->swiglu) {
-            if ((ex->swiglu != 1 && ex->swiglu != 2) || nw != 2 || ws[0].type != ws[1].type || ws[0].M != ws[1].M || ws[0].M <= 0 || ex->residual[0] || ex->residual[1] ||
-                (size_t) N * K * 5 / 4 + (norm_w ? (size_t) N * K * 4 : 0) + 4096 > 150 * 1024)
-                return fail(QMM_EUNSUPPORTED, "qmm_mul_mat_group_ex: swiglu wants two matrices of one type and shape, no residuals, all tokens in one launch");
-        }
+    if (ex) {                                                    // few-token extras: validated by the plan header, whatever N
+        char msg[160];
+        const int rc = matvec_extras_check(ws, nw, K, N, ex, msg, sizeof(msg));
+        if (rc) return fail(rc, "%s", msg);
     }
-    auto extras = [&](MatvecGroup & g, const int * src_index, int64_t n0) {      // residual pointers of the matrices in g, norm parameters
-        if (!ex) return;
-        for (int k = 0; k < g.n; ++k) g.res[k] = ex->residual[src_index[k]] ? ex->residual[src_index[k]] + n0 * g.ldd[k] : nullptr;
-        g.norm_w = norm_w;
-        g.norm_eps = ex->norm_eps;
-        g.swiglu = ex->swiglu;
-    };
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->s(stream);
     for (int i = 0; i < nw; ++i) {
@@ -652,70 +584,17 @@ static int mul_mat_group_impl(qmm_ctx * c, const qmm_weight * ws, int nw, int64_
         int rc = chain_launch(c);
         if (rc) return rc;
     }
-    if (N <= QMM_MATVEC_MAX_N && nw >= 2 && nw <= MV_MAX_GROUP && c->mv_kmix) {
-        // K-quant matrices of different types share the Q8_K activations: one mixed-type launch for the whole group
-        bool kq = true, mixed = false;
-        int n_k = 0, n_80 = 0;                                    // K-quant matrices (Q8_K activations), Q8_0 matrices (Q8_0 activations)
-        for (int i = 0; i < nw; ++i) {
-            const bool k = ws[i].type == T_Q4_K || ws[i].type == T_Q5_K || ws[i].type == T_Q6_K || ws[i].type == T_Q6_KP;
-            const bool q = ws[i].type == T_Q8_0 || ws[i].type == T_Q8_0P;
-            n_k += k;  n_80 += q;
-            kq = kq && (k || q) && ws[i].M > 0;
-            mixed = mixed || ws[i].type != ws[0].type;
-        }
-        // both activation formats in one group (Mixtral's q in Q4_K with k / v in Q8_0): one launch that stages the row twice
-        const bool q80 = n_80 > 0;
-        if (q80) kq = kq && n_k > 0 && c->mv_kmix > 1 && N <= 4 && !norm_w && !(ex && ex->swiglu) && (size_t) N * K * 21 / 8 + 4096 <= 150 * 1024;
-        if (kq && mixed && (size_t) N * K * 11 / 8 + 4096 <= 150 * 1024) {
-            MatvecGroup g;
-            memset(&g, 0, sizeof(g));
-            int rows = 0, idx[MV_MAX_GROUP];
-            for (int i = 0; i < nw; ++i) {
-                g.w[i] = (const uint8_t *) ws[i].w;  g.dst[i] = ws[i].dst;  g.row_bytes[i] = ws[i].w_row_bytes;  g.ldd[i] = ws[i].ldd;
-                g.type[i] = ws[i].type;
-                rows += (int) ws[i].M;
-                g.row_end[i] = rows;
-                idx[i] = i;
-            }
-            g.n = nw;
-            extras(g, idx, 0);
-            return launch_kmix(c, st, g, x, ldx, (int) K, (int) N, q80);
-        }
-    }
     if (N <= QMM_MATVEC_MAX_N) {
-        // one launch per run of same-type weights (they share the in-kernel activation quantization)
-        int i = 0;
-        while (i < nw) {
-            MatvecGroup g;
-            memset(&g, 0, sizeof(g));
-            int rows = 0, j = i, idx[MV_MAX_GROUP];
-            while (j < nw && ws[j].type == ws[i].type && g.n < MV_MAX_GROUP) {
-                if (ws[j].M > 0) {
-                    idx[g.n] = j;
-                    g.w[g.n] = (const uint8_t *) ws[j].w;
-                    g.dst[g.n] = ws[j].dst;
-                    g.row_bytes[g.n] = ws[j].w_row_bytes;
-                    g.ldd[g.n] = ws[j].ldd;
-                    rows += (int) ws[j].M;
-                    g.row_end[g.n] = rows;
-                    g.n++;
-                }
-                ++j;
+        // few tokens: the plan (qmm_matvec_plan.h) lists the launches, run by run of the group's matrices; this executes it
+        const MatvecRules rules = matvec_rules(c);
+        for (int first = 0; first < nw;) {
+            const MatvecPlan plan = matvec_group_plan(rules, ws, nw, K, N, ex, first);
+            for (int k = 0; k < plan.n; ++k) {
+                const MatvecLaunch & l = plan.launch[k];
+                int rc = run_matvec(c, st, l, matvec_group(ws, l.idx, l.row_end, l.n, l.n0, ex), x + l.n0 * ldx, ldx);
+                if (rc) return rc;
             }
-            if (g.n > 0) {
-                // tokens that do not fit LDS together are processed in sub-batches
-                int n_at_once = (int) N;
-                while (n_at_once > 1 && ((size_t) n_at_once * K * 5 / 4 + 4096) > 150 * 1024) n_at_once = (n_at_once + 1) / 2;
-                for (int64_t n0 = 0; n0 < N; n0 += n_at_once) {
-                    const int nn = (int) ((N - n0) < n_at_once ? (N - n0) : n_at_once);
-                    MatvecGroup gg = g;
-                    for (int k = 0; k < gg.n; ++k) gg.dst[k] = g.dst[k] + n0 * g.ldd[k];
-                    extras(gg, idx, n0);
-                    int rc = matvec_any(c, st, ws[i].type, gg, x + n0 * ldx, ldx, (int) K, nn);
-                    if (rc) return rc;
-                }
-            }
-            i = j;
+            first = plan.next;
         }
         return QMM_OK;
     }
@@ -845,16 +724,24 @@ int qmm_mul_mat(qmm_ctx * c, int type, const void * w, int64_t rb, int64_t K, in
     return qmm_mul_mat_group(c, &ws, 1, K, x, N, ldx, stream);
 }
 
+// what the MUL_MAT_ID entry points check alike (who: the entry point, for the messages; second: its second tensor and destination are there)
+static int check_mm_id(const qmm_ctx * c, const char * who, bool second, int type, const void * as, int64_t rb, int64_t expert_bytes, int64_t K, const float * b, int64_t ne11,
+                       int64_t b_nb1, int64_t b_nb2, int64_t ids_nb1, int64_t n_used, int64_t d_nb1, int64_t d_nb2) {
+    if (!c) return fail(QMM_EINVAL, "null ctx");
+    if (!second) return fail(QMM_EINVAL, "%s: second tensor missing", who);
+    const int rc = check_mm(type, as, rb, K, b, K, who);
+    if (rc) return rc;
+    if (b_nb1 % 16 || b_nb2 % 16 || ids_nb1 % 4 || d_nb1 % 4 || d_nb2 % 4 || expert_bytes % 2 || (ne11 != 1 && ne11 != n_used)) return fail(QMM_EINVAL, "%s: strides / ne11", who);
+    return QMM_OK;
+}
+
 int qmm_mul_mat_id(qmm_ctx * c, int type, const void * as, int64_t rb, int64_t expert_bytes,
                    int64_t K, int64_t M, int64_t n_expert,
                    const float * b, int64_t ne11, int64_t b_nb1, int64_t b_nb2,
                    const int32_t * ids, int64_t n_used, int64_t n_tokens, int64_t ids_nb1,
                    float * dst, int64_t d_nb1, int64_t d_nb2, void * stream) {
-    if (!c) return fail(QMM_EINVAL, "null ctx");
-    int rc = check_mm(type, as, rb, K, b, K, "qmm_mul_mat_id");
+    const int rc = check_mm_id(c, "qmm_mul_mat_id", true, type, as, rb, expert_bytes, K, b, ne11, b_nb1, b_nb2, ids_nb1, n_used, d_nb1, d_nb2);
     if (rc) return rc;
-    if (b_nb1 % 16 || b_nb2 % 16 || ids_nb1 % 4 || d_nb1 % 4 || d_nb2 % 4 || expert_bytes % 2 || (ne11 != 1 && ne11 != n_used))
-        return fail(QMM_EINVAL, "qmm_mul_mat_id: strides / ne11");
     if (n_tokens <= 0 || n_used <= 0 || M <= 0) return QMM_OK;
     HIP_TRY(hipSetDevice(c->device));
     QMM_CHAIN_FLUSH(c);
@@ -869,12 +756,8 @@ int qmm_mul_mat_id_pair(qmm_ctx * c, int type, const void * as0, const void * as
                         const float * b, int64_t ne11, int64_t b_nb1, int64_t b_nb2,
                         const int32_t * ids, int64_t n_used, int64_t n_tokens, int64_t ids_nb1,
                         float * dst0, float * dst1, int64_t d_nb1, int64_t d_nb2, void * stream) {
-    if (!c) return fail(QMM_EINVAL, "null ctx");
-    if (!as1 || !dst1) return fail(QMM_EINVAL, "qmm_mul_mat_id_pair: second tensor missing");
-    int rc = check_mm(type, as0, rb, K, b, K, "qmm_mul_mat_id_pair");
+    const int rc = check_mm_id(c, "qmm_mul_mat_id_pair", as1 && dst1, type, as0, rb, expert_bytes, K, b, ne11, b_nb1, b_nb2, ids_nb1, n_used, d_nb1, d_nb2);
     if (rc) return rc;
-    if (b_nb1 % 16 || b_nb2 % 16 || ids_nb1 % 4 || d_nb1 % 4 || d_nb2 % 4 || expert_bytes % 2 || (ne11 != 1 && ne11 != n_used))
-        return fail(QMM_EINVAL, "qmm_mul_mat_id_pair: strides / ne11");
     if (n_tokens <= 0 || n_used <= 0 || M <= 0) return QMM_OK;
     HIP_TRY(hipSetDevice(c->device));
     QMM_CHAIN_FLUSH(c);
@@ -885,7 +768,7 @@ int qmm_mul_mat_id_pair(qmm_ctx * c, int type, const void * as0, const void * as
 }
 
 int qmm_mul_mat_id_swiglu_supported(int64_t n_used, int64_t n_tokens) {
-    return n_used > 0 && n_tokens > 0 && n_used * n_tokens <= MOE_MATVEC_MAX_PAIRS;
+    return moe_runs_as_matvec(n_used, n_tokens);
 }
 
 int qmm_mul_mat_id_swiglu(qmm_ctx * c, int type, const void * as_gate, const void * as_up, int64_t rb, int64_t expert_bytes,
@@ -893,23 +776,14 @@ int qmm_mul_mat_id_swiglu(qmm_ctx * c, int type, const void * as_gate, const voi
                           const float * b, int64_t ne11, int64_t b_nb1, int64_t b_nb2,
                           const int32_t * ids, int64_t n_used, int64_t n_tokens, int64_t ids_nb1,
                           float * dst, int64_t d_nb1, int64_t d_nb2, void * stream) {
-    if (!c) return fail(QMM_EINVAL, "null ctx");
-    if (!as_up || !dst) return fail(QMM_EINVAL, "qmm_mul_mat_id_swiglu: second tensor missing");
-    int rc = check_mm(type, as_gate, rb, K, b, K, "qmm_mul_mat_id_swiglu");
+    const int rc = check_mm_id(c, "qmm_mul_mat_id_swiglu", as_up && dst, type, as_gate, rb, expert_bytes, K, b, ne11, b_nb1, b_nb2, ids_nb1, n_used, d_nb1, d_nb2);
     if (rc) return rc;
-    if (b_nb1 % 16 || b_nb2 % 16 || ids_nb1 % 4 || d_nb1 % 4 || d_nb2 % 4 || expert_bytes % 2 || (ne11 != 1 && ne11 != n_used))
-        return fail(QMM_EINVAL, "qmm_mul_mat_id_swiglu: strides / ne11");
     if (!qmm_mul_mat_id_swiglu_supported(n_used, n_tokens)) return fail(QMM_EUNSUPPORTED, "qmm_mul_mat_id_swiglu: more than %d (token, slot) pairs", MOE_MATVEC_MAX_PAIRS);
     if (M <= 0) return QMM_OK;
     HIP_TRY(hipSetDevice(c->device));
     QMM_CHAIN_FLUSH(c);
     c->id_calls++;
-    hipStream_t st = c->s(stream);
-#define QMM_MVIDS(TT)                                                                                                                  \
-    return launch_matvec_id_swiglu<TT>(c, st, as_gate, as_up, rb, expert_bytes, (int) K, (int) M, (int) n_expert, b, (int) ne11, b_nb1 / 4, b_nb2 / 4, ids, \
-                                       (int) n_used, (int) n_tokens, ids_nb1 / 4, dst, d_nb1 / 4, d_nb2 / 4)
-    QMM_FOR_TYPE(type, QMM_MVIDS)
-#undef QMM_MVIDS
+    return moe_mul_mat_id(c, c->s(stream), type, as_gate, rb, expert_bytes, K, M, n_expert, b, ne11, b_nb1, b_nb2, ids, n_used, n_tokens, ids_nb1, dst, d_nb1, d_nb2, as_up, nullptr, MOE_MV_SWIGLU);
 }
 
 int qmm_chain_begin(qmm_ctx * c) {

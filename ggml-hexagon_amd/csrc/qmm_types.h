@@ -1,5 +1,5 @@
 // qmm_types.h — the weight type ids and the run-time views of the type table.  Plain C++ (no HIP): qmm_device.hiph includes it for
-// the kernels, qmm_prefill_plan.h for the host-side launch plan, and a host compiler alone can read both.
+// the kernels, qmm_prefill_plan.h and qmm_matvec_plan.h for the host-side launch plans, and a host compiler alone can read both.
 #pragma once
 
 #include <stdint.h>
@@ -29,7 +29,7 @@ QMM_HD inline bool type_known(int t) {
     return t == T_Q4_0 || t == T_Q4_1 || t == T_Q5_0 || t == T_Q5_1 || t == T_Q8_0 || t == T_Q2_K || t == T_Q3_K || t == T_Q4_K || t == T_Q5_K ||
            t == T_Q6_K || t == T_IQ4_NL || t == T_IQ4_XS;
 }
-QMM_HD inline int type_blck(int t) { t = type_base(t); return (t == T_Q2_K || t == T_Q3_K || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_IQ4_XS) ? 256 : 32; }
+QMM_HD constexpr int type_blck(int t) { t = type_base(t); return (t == T_Q2_K || t == T_Q3_K || t == T_Q4_K || t == T_Q5_K || t == T_Q6_K || t == T_IQ4_XS) ? 256 : 32; }
 QMM_HD inline int type_tsize(int t) {
     switch (type_base(t)) {
         case T_Q4_0: return 18; case T_Q4_1: return 20; case T_Q5_0: return 22; case T_Q5_1: return 24; case T_Q8_0: return 34; case T_IQ4_NL: return 18;
@@ -37,6 +37,6 @@ QMM_HD inline int type_tsize(int t) {
     }
 }
 // activation format the CPU backend dots the type against (type_traits_cpu[].vec_dot_type, ggml-cpu.c:256-...)
-QMM_HD inline int type_act(int t) { t = type_base(t); return type_blck(t) == 256 ? T_Q8_K : (t == T_Q4_1 || t == T_Q5_1) ? T_Q8_1 : T_Q8_0; }
+QMM_HD constexpr int type_act(int t) { t = type_base(t); return type_blck(t) == 256 ? T_Q8_K : (t == T_Q4_1 || t == T_Q5_1) ? T_Q8_1 : T_Q8_0; }
 
 } // namespace qmm
