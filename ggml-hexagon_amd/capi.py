@@ -10,12 +10,12 @@ from . import build as _build
 Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 2, 8, 12, 13, 14, 15
 Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, IQ4_NL, IQ4_XS = 3, 6, 7, 10, 11, 20, 23
 ACT_REF, ACT_X86 = 0, 1
-PREC_BF16, PREC_F16_Q8 = 0, 1
+PREC_BF16, PREC_F16_Q8, PREC_Q8_EXACT = 0, 1, 2
 MATVEC_MAX_N = 8
 
 EXPORTS = [
     "qmm_abi_version", "qmm_last_error", "qmm_device_count", "qmm_create", "qmm_destroy", "qmm_device", "qmm_stream",
-    "qmm_device_info", "qmm_set_act_mode", "qmm_set_precision", "qmm_malloc", "qmm_free", "qmm_host_malloc", "qmm_host_free", "qmm_memcpy_h2d",
+    "qmm_device_info", "qmm_set_act_mode", "qmm_set_precision", "qmm_q8_exact_supported", "qmm_malloc", "qmm_free", "qmm_host_malloc", "qmm_host_free", "qmm_memcpy_h2d",
     "qmm_memcpy_d2h", "qmm_memcpy_d2d", "qmm_memset", "qmm_synchronize", "qmm_memcpy2d_d2d", "qmm_event_create",
     "qmm_event_destroy", "qmm_event_record", "qmm_stream_wait_event", "qmm_event_synchronize", "qmm_event_create_timing", "qmm_event_elapsed_ms", "qmm_memcpy_h2d_async",
     "qmm_memcpy_d2h_async", "qmm_row_size", "qmm_planar_type", "qmm_repack_rows", "qmm_dequantize",
@@ -86,6 +86,7 @@ def load_library() -> C.CDLL:
     lib.qmm_device_info.argtypes = [v, C.c_char_p, sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(i32)]
     lib.qmm_set_act_mode.argtypes = [v, i32]
     lib.qmm_set_precision.argtypes = [v, i32]
+    lib.qmm_q8_exact_supported.argtypes = [i32, i64]
     lib.qmm_malloc.restype = v
     lib.qmm_malloc.argtypes = [v, sz]
     lib.qmm_free.argtypes = [v, v]
@@ -174,6 +175,10 @@ class Qmm:
 
     def set_precision(self, p):
         self._chk(self.lib.qmm_set_precision(self.ctx, p))
+
+    def q8_exact_supported(self, t, k):
+        """1 when a prefill mul_mat of this weight type and K is exact in PREC_Q8_EXACT, 0 when that mode runs it as PREC_F16_Q8"""
+        return self.lib.qmm_q8_exact_supported(t, k)
 
     def synchronize(self):
         self._chk(self.lib.qmm_synchronize(self.ctx, self._stream()))

@@ -39,7 +39,7 @@ plugin_switches read_plugin_switches() {
     p.no_pinned = v[SW_NO_PINNED];  p.debug = v[SW_DEBUG];
     p.router_norm_off = v[SW_ROUTER_NORM_OFF];  p.prep_norm_off = v[SW_PREP_NORM_OFF];  p.router_logits_off = v[SW_ROUTER_LOGITS_OFF];
     p.moe_swiglu_off = v[SW_MOE_SWIGLU_OFF];  p.moe_combine_norm_off = v[SW_MOE_COMBINE_NORM_OFF];
-    p.prec_set = v.is_set(SW_PREC);  p.prec_bf16 = prec_is_bf16(v.str(SW_PREC));
+    p.prec_set = v.is_set(SW_PREC);  p.prec_bf16 = prec_is_bf16(v.str(SW_PREC));  p.prec_q8 = prec_is_q8(v.str(SW_PREC));
     p.virtual_devices = v.is_set(SW_VIRTUAL_DEVICES) ? atoi(v.str(SW_VIRTUAL_DEVICES)) : 0;
     return p;
 }

@@ -38,7 +38,7 @@ struct plugin_switches {
     bool chain, rccl, timing;                                          // on when set to a non-zero number
     bool no_pinned, debug;                                             // on by presence
     bool router_norm_off, prep_norm_off, router_logits_off, moe_swiglu_off, moe_combine_norm_off;
-    bool prec_set, prec_bf16;                                          // GGML_MI355X_PREC present at all / asks for bf16
+    bool prec_set, prec_bf16, prec_q8;                                 // GGML_MI355X_PREC present at all / asks for bf16 / for the Q8-exact mode
     int  virtual_devices;                                              // <= 0: the physical devices
 };
 plugin_switches read_plugin_switches();

@@ -264,7 +264,7 @@ qmm_ctx * qmm_create(int device) {
     c->skinny         = sw[qmm_sw::SW_SKINNY];
     if (sw[qmm_sw::SW_SKINNY_MAXN]) c->skinny_max_n = c->skinny_max_n_few = sw[qmm_sw::SW_SKINNY_MAXN];
     if (sw.is_set(qmm_sw::SW_ABLATE)) { int v = sw[qmm_sw::SW_ABLATE]; (void) hipMemcpyToSymbol(HIP_SYMBOL(g_mfma_dbg), &v, sizeof(int)); }
-    c->prec           = qmm_sw::prec_is_bf16(sw.str(qmm_sw::SW_PREC)) ? QMM_PREC_BF16 : QMM_PREC_F16_Q8;
+    c->prec           = qmm_sw::prec_is_bf16(sw.str(qmm_sw::SW_PREC)) ? QMM_PREC_BF16 : qmm_sw::prec_is_q8(sw.str(qmm_sw::SW_PREC)) ? QMM_PREC_Q8_EXACT : QMM_PREC_F16_Q8;
     return c;
 }
 
@@ -309,10 +309,11 @@ int qmm_set_act_mode(qmm_ctx * c, int m) {
     return QMM_OK;
 }
 int qmm_set_precision(qmm_ctx * c, int p) {
-    if (!c || (p != QMM_PREC_BF16 && p != QMM_PREC_F16_Q8)) return fail(QMM_EINVAL, "bad precision");
+    if (!c || (p != QMM_PREC_BF16 && p != QMM_PREC_F16_Q8 && p != QMM_PREC_Q8_EXACT)) return fail(QMM_EINVAL, "bad precision");
     c->prec = p;
     return QMM_OK;
 }
+int qmm_q8_exact_supported(int type, int64_t K) { return q8x_supports(type, K) ? 1 : 0; }
 
 void * qmm_malloc(qmm_ctx * c, size_t bytes) {
     if (!c) return nullptr;

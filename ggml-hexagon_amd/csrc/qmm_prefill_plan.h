@@ -26,7 +26,8 @@ enum : unsigned { PF_GATHER = 1,      // MUL_MAT_ID: rows gathered per expert, s
                   PF_SWIGLU = 2,      // the prep forms silu(x) * x2 (qmm_mul_mat_swiglu_in)
                   PF_NORM   = 4 };    // the prep forms rms_norm(x [+ add]) * w (qmm_mul_mat_group_ex)
 
-enum PrefillKernel { PK_NONE, PK_LDS_TILE, PK_SKINNY, PK_REGB, PK_WIDE, PK_R64_4, PK_R64_8, PK_R64S };
+enum PrefillKernel { PK_NONE, PK_LDS_TILE, PK_SKINNY, PK_REGB, PK_WIDE, PK_R64_4, PK_R64_8, PK_R64S,
+                     PK_Q8X };         // QMM_PREC_Q8_EXACT: mfma_q8x_kernel<T> (qmm_mfma_q8x.hiph)
 
 struct PrefillPlan {
     // a run of 2..4 matrices that cannot be one launch: the caller plans and runs each matrix on its own (the first prepares the
@@ -48,6 +49,7 @@ struct PrefillPlan {
     // the activation prep
     int      act, perm;       // prep_act_kernel<act, f16, perm> / prep_act_q8k_kernel<perm, ...>
     bool     prep_reg;        // prep_act_q8k_kernel (registers) instead of prep_act_kernel (LDS staging)
+    bool     prep_q8x;        // prep_act_q8x_kernel: the Q8_K rows themselves, int8 [N, K] at o_xh and d f32 [N, K / 256] at o_scale
     bool     prep_x2, prep_norm;   // the prep forms the SwiGLU product / the RMS norm (never for gathered rows)
     unsigned prep_grid, prep_block;
     size_t   prep_lds;
@@ -80,6 +82,17 @@ inline int prefill_perm(const PrefillRules & r, int type) {
     if (type == T_Q4_0 || type == T_Q4_1 || type == T_Q5_0 || type == T_Q5_1 || type == T_IQ4_NL || type == T_IQ4_XS) return 4;
     return 0;
 }
+
+// QMM_PREC_Q8_EXACT covers the K-quant formats whose sub-block scale is an integer that can go into the weight before the int8 MFMA
+// (wire layout; planar Q6_K rows, every other type and MUL_MAT_ID run as in QMM_PREC_F16_Q8)
+inline bool q8x_supports(int type, int64_t K) { return (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K) && K > 0 && K % 256 == 0; }
+// ... and the rules such a call, or any call of another mode, is planned by
+inline PrefillRules prefill_effective_rules(PrefillRules r, int type, int64_t K, bool gather) {
+    if (r.prec == QMM_PREC_Q8_EXACT && (gather || !q8x_supports(type, K))) r.prec = QMM_PREC_F16_Q8;
+    return r;
+}
+constexpr int Q8X_ROWS = 128, Q8X_TOKENS = 64;      // tile of a workgroup of mfma_q8x_kernel: 4 waves of 32 rows each on the same 64 tokens
+constexpr int Q8X_KEY  = 1;                         // one operand for the three formats (the other modes' keys are 0 or >= 6)
 
 namespace plan_detail {
 
@@ -214,10 +227,34 @@ inline void plan_kernel(PrefillPlan & p, const PrefillRules & r, int type, const
     else                                                  regb(4, 32, 128, 4 * nty);
 }
 
+// QMM_PREC_Q8_EXACT on a supported type: the Q8_K rows as they are (prep_act_q8x_kernel, four rows per workgroup), then one
+// mfma_q8x_kernel<T> launch per matrix over 128-row x 64-token tiles.  No split-K, no LDS; a group is one launch per matrix on one prep.
+inline PrefillPlan plan_q8x(int type, const int64_t * M, int n, int64_t K, int64_t N, unsigned flags) {
+    PrefillPlan p = {};
+    p.act = T_Q8_K;  p.Kp = (int) K;  p.key = Q8X_KEY;  p.ksplit = 1;  p.prep_q8x = true;
+    p.prep_grid = (unsigned) ((N + 3) / 4);  p.prep_block = 256;
+    snprintf(p.prep_label, sizeof(p.prep_label), "prep_act_q8x_kernel");
+    if (flags & (PF_SWIGLU | PF_NORM)) p.unsupported = "SwiGLU input / fused norm: only in the default (f16 on Q8 activations) prefill mode";
+    p.rows_vec4 = true;
+    for (int i = 0; i < n; ++i) { p.tiles_x += (int) ((M[i] + Q8X_ROWS - 1) / Q8X_ROWS);  p.mtot += (int) M[i];  p.rows_vec4 = p.rows_vec4 && M[i] % 4 == 0; }
+    p.n_tiles_y = (int) ((N + Q8X_TOKENS - 1) / Q8X_TOKENS);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~(size_t) 255; return o; };
+    p.o_xh = take((size_t) N * K);  p.o_scale = take((size_t) N * (K / 256) * 4);  p.o_part = off;
+    p.ws_total = off + 256;
+    if (n > 1) { p.per_matrix = true;  p.kernel = PK_NONE;  return p; }
+    p.kernel = PK_Q8X;  p.ta = type;
+    p.grid[0] = (unsigned) p.tiles_x;  p.grid[1] = (unsigned) p.n_tiles_y;  p.grid[2] = 1;  p.block = 256;
+    snprintf(p.label, sizeof(p.label), "mfma_q8x_kernel<%d>", type);
+    return p;
+}
+
 } // namespace plan_detail
 
 // the prep key of one matrix alone: mul_mat_group_impl cuts a group into runs of one type and one key
-inline int prefill_prep_key(const PrefillRules & r, int type, int64_t M, int64_t K, int64_t N) {
+inline int prefill_prep_key(const PrefillRules & r0, int type, int64_t M, int64_t K, int64_t N) {
+    const PrefillRules r = prefill_effective_rules(r0, type, K, false);
+    if (r.prec == QMM_PREC_Q8_EXACT) return Q8X_KEY;
     return plan_detail::plan_key(r, type, prefill_perm(r, type), plan_detail::mfma_use_skinny(r, type, N, M), K);
 }
 
@@ -226,10 +263,12 @@ inline int prefill_prep_key(const PrefillRules & r, int type, int64_t M, int64_t
 // Plain MUL_MATs that share src1 and the weight type (attn_q / attn_k / attn_v at prefill): one launch of the tiled kernel
 // over the row tiles of all of them and one reduce, instead of a launch (and, with split-K, a reduce) per matrix; the 1024-row
 // matrices alone are 16 tiles each.  Falls back to one call per matrix where the few-token kernel or a smaller tile applies.
-inline PrefillPlan prefill_plan(const PrefillRules & r, int type, const int64_t * M, int n, int64_t K, int64_t N, int64_t n_expert, unsigned flags) {
+inline PrefillPlan prefill_plan(const PrefillRules & r0, int type, const int64_t * M, int n, int64_t K, int64_t N, int64_t n_expert, unsigned flags) {
     using namespace plan_detail;
     PrefillPlan p = {};
     const bool gather = flags & PF_GATHER;
+    const PrefillRules r = prefill_effective_rules(r0, type, K, gather);
+    if (r.prec == QMM_PREC_Q8_EXACT) return plan_q8x(type, M, n, K, N, flags);
     plan_prep(p, r, type, K, N, flags);
     const bool skinny = mfma_use_skinny(r, type, N, M[0], n_expert);
     p.key = gather ? 0 : prefill_prep_key(r, type, M[0], K, N);
