@@ -212,7 +212,7 @@ rms_norm_kernel(const char * __restrict__ x, const float * __restrict__ w, char 
 }
 
 // ggml_compute_forward_norm_f32 (ggml-cpu.c:6183-6232), the LayerNorm of GPT-2 / Falcon / Phi-style models: mean over the row,
-// then the variance of the centred values, y = (x - mean) / sqrt(var + eps).  One block per row, two passes over L2.
+// then the variance of the centred values, y = (x - mean) / sqrt(var + eps).  One block per row, four passes over L2.
 __global__ void __launch_bounds__(256)
 norm_kernel(const char * __restrict__ x, char * __restrict__ y, const Shape sx, const Shape sy, const float eps) {
     __shared__ float red[4];
@@ -223,7 +223,13 @@ norm_kernel(const char * __restrict__ x, char * __restrict__ y, const Shape sx, 
     const uint32_t n = (uint32_t) sx.ne[0];
     float sum = 0.0f;
     for (uint32_t i = threadIdx.x; i < n; i += 256) sum += px[i];
-    const float mean = block_reduce<false>(sum, red) / (float) n;
+    float mean = block_reduce<false>(sum, red) / (float) n;
+    // the CPU takes this sum in double.  One f32 sum of n values near m is good to about n ulp(n m): for a row with a mean far from zero
+    // (|mean| / sigma ~ 1000) that is 1e-4 of sigma and more, which after centring is the signal.  A second pass adds the mean of what the
+    // first left over: the leftovers are of the size of sigma, so their sum is exact to ~1e-7 sigma
+    float rest = 0.0f;
+    for (uint32_t i = threadIdx.x; i < n; i += 256) rest += px[i] - mean;
+    mean += block_reduce<false>(rest, red) / (float) n;
     float sum2 = 0.0f;
     for (uint32_t i = threadIdx.x; i < n; i += 256) { const float v = px[i] - mean; sum2 += v * v; }
     const float scale = 1.0f / sqrtf(block_reduce<false>(sum2, red) / (float) n + eps);
@@ -1841,12 +1847,14 @@ bool sup_mul_mat_f(const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor 
 // ------------------------------------------------------------------------------------------------ launchers
 
 template <int OP>
-int launch_binary(hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d) {
+int launch_binary(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d) {
     const uint32_t rows = (uint32_t) nrows(d);
     const bool vec = d->ne[0] % 4 == 0 && b->ne[0] == d->ne[0] && b->nb[0] == 4 && aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(d, 16);
     const uint32_t per_row = (uint32_t) (vec ? d->ne[0] / 4 : d->ne[0]);
     const uint32_t rpb = per_row >= 256 ? 1 : 256 / per_row;
     const dim3 grid((rows + rpb - 1) / rpb);
+    if (vec) QMM_TRACE(ctx, "binary_kernel<vec>");
+    else     QMM_TRACE(ctx, "binary_kernel<scalar>");
     if (vec) hipLaunchKernelGGL((binary_kernel<OP, true>), grid, dim3(256), 0, st, (const char *) a->data, (const char *) b->data, (char *) d->data,
                                 shape_of(a), shape_of(b), shape_of(d), rows);
     else     hipLaunchKernelGGL((binary_kernel<OP, false>), grid, dim3(256), 0, st, (const char *) a->data, (const char *) b->data, (char *) d->data,
@@ -1856,9 +1864,10 @@ int launch_binary(hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, co
 }
 
 template <int OP, bool MUL2>
-int launch_unary(hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d, float p) {
+int launch_unary(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d, float p) {
     const uint32_t n = (uint32_t) nelements(d);
     if (n == 0) return QMM_OK;
+    QMM_TRACE(ctx, "unary_kernel");
     hipLaunchKernelGGL((unary_kernel<OP, MUL2>), dim3((n + 1023) / 1024), dim3(256), 0, st, (const float *) a->data,
                        b ? (const float *) b->data : nullptr, (float *) d->data, n, p);
     HIP_TRY(hipGetLastError());
@@ -1866,41 +1875,45 @@ int launch_unary(hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, con
 }
 
 template <typename TS, typename TD>
-int launch_cpy_t(hipStream_t st, const qmm_tensor * a, const qmm_tensor * d) {
+int launch_cpy_t(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * d) {
     const uint32_t n = (uint32_t) nelements(a);
     // transposed source into dense rows (the V-cache store): 2-D, same extents, src dense along dim 1, dst dense along dim 0
     if (a->ne[2] == 1 && a->ne[3] == 1 && d->ne[2] == 1 && d->ne[3] == 1 && a->ne[0] == d->ne[0] && a->ne[1] == d->ne[1] &&
         a->nb[1] == (int64_t) sizeof(TS) && d->nb[0] == (int64_t) sizeof(TD) && a->ne[0] >= 32 && a->ne[1] >= 8) {
+        QMM_TRACE(ctx, "cpy_transpose_kernel");
         hipLaunchKernelGGL((cpy_transpose_kernel<TS, TD>), dim3((unsigned) ((a->ne[0] + 31) / 32), (unsigned) ((a->ne[1] + 31) / 32)), dim3(256), 0, st,
                            (const char *) a->data, (char *) d->data, (uint32_t) a->ne[0], (uint32_t) a->ne[1], a->nb[0], d->nb[1]);
     } else {
+        QMM_TRACE(ctx, "cpy_kernel");
         hipLaunchKernelGGL((cpy_kernel<TS, TD>), dim3((n + 255) / 256), dim3(256), 0, st, (const char *) a->data, (char *) d->data, shape_of(a),
                            shape_of(d), n);
     }
     HIP_TRY(hipGetLastError());
     return QMM_OK;
 }
-int launch_cpy(hipStream_t st, const qmm_tensor * a, const qmm_tensor * d) {
+int launch_cpy(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * d) {
     if (nelements(a) == 0) return QMM_OK;
     if (a->type == d->type && contiguous(a) && contiguous(d)) {
+        QMM_TRACE(ctx, "memcpy");
         if (a->data != d->data) HIP_TRY(hipMemcpyAsync(d->data, a->data, (size_t) nelements(a) * esize(a->type), hipMemcpyDeviceToDevice, st));
         return QMM_OK;
     }
-    if (a->type == G_F32 && d->type == G_F32) return launch_cpy_t<float, float>(st, a, d);
-    if (a->type == G_F32 && d->type == G_F16) return launch_cpy_t<float, __half>(st, a, d);
-    if (a->type == G_F16 && d->type == G_F16) return launch_cpy_t<__half, __half>(st, a, d);
-    return launch_cpy_t<__half, float>(st, a, d);
+    if (a->type == G_F32 && d->type == G_F32) return launch_cpy_t<float, float>(ctx, st, a, d);
+    if (a->type == G_F32 && d->type == G_F16) return launch_cpy_t<float, __half>(ctx, st, a, d);
+    if (a->type == G_F16 && d->type == G_F16) return launch_cpy_t<__half, __half>(ctx, st, a, d);
+    return launch_cpy_t<__half, float>(ctx, st, a, d);
 }
 
 template <int T>
-int launch_get_rows_q(hipStream_t st, const qmm_tensor * a, const qmm_tensor * ids, const qmm_tensor * d) {
+int launch_get_rows_q(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * ids, const qmm_tensor * d) {
+    QMM_TRACE(ctx, "get_rows_q_kernel<%d>", T);
     hipLaunchKernelGGL((get_rows_q_kernel<T>), dim3((unsigned) nrows(d)), dim3(256), 0, st, (const uint8_t *) a->data, (const char *) ids->data,
                        (char *) d->data, shape_of(a), shape_of(ids), shape_of(d));
     HIP_TRY(hipGetLastError());
     return QMM_OK;
 }
 
-int launch_mul_mat_f(hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d) {
+int launch_mul_mat_f(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d) {
     MmArgs g;
     g.a = (const char *) a->data;  g.b = (const char *) b->data;  g.d = (char *) d->data;
     g.a_nb1 = a->nb[1]; g.a_nb2 = a->nb[2]; g.a_nb3 = a->nb[3];
@@ -1912,23 +1925,25 @@ int launch_mul_mat_f(hipStream_t st, const qmm_tensor * a, const qmm_tensor * b,
     if (a->type == G_F16) {
         const dim3 grid((g.M + MM_T - 1) / MM_T, (g.N + MM_T - 1) / MM_T, batch);
         const bool vec = aligned_to(a, 16) && aligned_to(b, 16);
-        if (vec) hipLaunchKernelGGL((mul_mat_f16_kernel<true>), grid, dim3(256), 0, st, g);
-        else     hipLaunchKernelGGL((mul_mat_f16_kernel<false>), grid, dim3(256), 0, st, g);
+        if (vec) { QMM_TRACE(ctx, "mul_mat_f16_kernel<vec>");    hipLaunchKernelGGL((mul_mat_f16_kernel<true>), grid, dim3(256), 0, st, g); }
+        else     { QMM_TRACE(ctx, "mul_mat_f16_kernel<scalar>"); hipLaunchKernelGGL((mul_mat_f16_kernel<false>), grid, dim3(256), 0, st, g); }
     } else {
         const int64_t e = (int64_t) g.M * g.N;
-        if (e <= 2048 && g.K >= 1024) hipLaunchKernelGGL(mul_mat_dot_block_kernel, dim3((unsigned) e, 1, batch), dim3(DOT_T), 0, st, g);
-        else                          hipLaunchKernelGGL((mul_mat_dot_kernel<float>), dim3((unsigned) ((e + 3) / 4), 1, batch), dim3(256), 0, st, g);
+        if (e <= 2048 && g.K >= 1024) { QMM_TRACE(ctx, "mul_mat_dot_block_kernel"); hipLaunchKernelGGL(mul_mat_dot_block_kernel, dim3((unsigned) e, 1, batch), dim3(DOT_T), 0, st, g); }
+        else                          { QMM_TRACE(ctx, "mul_mat_dot_kernel");       hipLaunchKernelGGL((mul_mat_dot_kernel<float>), dim3((unsigned) ((e + 3) / 4), 1, batch), dim3(256), 0, st, g); }
     }
     HIP_TRY(hipGetLastError());
     return QMM_OK;
 }
 
 template <bool MUL, bool ADD>
-int launch_rms_norm_vec(hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * d, const qmm_tensor * sum,
+int launch_rms_norm_vec(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * d, const qmm_tensor * sum,
                         float eps) {
     const unsigned rows = (unsigned) nrows(d);
     const bool wide = rows < 256 || a->ne[0] > 256 * 16;
     const Shape sb = b ? shape_of(b) : shape_of(a), ss = sum ? shape_of(sum) : shape_of(d);
+    if (wide) QMM_TRACE(ctx, "rms_norm_vec_kernel<1024>");
+    else      QMM_TRACE(ctx, "rms_norm_vec_kernel<256>");
     if (wide)
         hipLaunchKernelGGL((rms_norm_vec_kernel<MUL, ADD, 1024>), dim3(rows), dim3(1024), 0, st, (const char *) a->data, b ? (const char *) b->data : nullptr,
                            w ? (const float *) w->data : nullptr, (char *) d->data, sum ? (char *) sum->data : nullptr, shape_of(a), sb, shape_of(d), ss, eps);
@@ -1940,16 +1955,17 @@ int launch_rms_norm_vec(hipStream_t st, const qmm_tensor * a, const qmm_tensor *
 }
 
 // y = rms_norm(a [+ b]) [* w]; `sum` receives a + b when b is given
-int launch_rms_norm(hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * d, const qmm_tensor * sum, float eps) {
+int launch_rms_norm(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * d, const qmm_tensor * sum, float eps) {
     if (eps < 0.0f) return fail(QMM_EINVAL, "RMS_NORM: eps < 0");
     const bool vec = a->ne[0] % 4 == 0 && a->ne[0] <= 1024 * 16 && aligned_to(a, 16) && aligned_to(d, 16) && (!w || (uintptr_t) w->data % 16 == 0) &&
                      (!b || (aligned_to(b, 16) && aligned_to(sum, 16)));
     if (vec) {
-        if (b) return w ? launch_rms_norm_vec<true, true>(st, a, b, w, d, sum, eps) : launch_rms_norm_vec<false, true>(st, a, b, w, d, sum, eps);
-        return w ? launch_rms_norm_vec<true, false>(st, a, b, w, d, sum, eps) : launch_rms_norm_vec<false, false>(st, a, b, w, d, sum, eps);
+        if (b) return w ? launch_rms_norm_vec<true, true>(ctx, st, a, b, w, d, sum, eps) : launch_rms_norm_vec<false, true>(ctx, st, a, b, w, d, sum, eps);
+        return w ? launch_rms_norm_vec<true, false>(ctx, st, a, b, w, d, sum, eps) : launch_rms_norm_vec<false, false>(ctx, st, a, b, w, d, sum, eps);
     }
     if (b) return fail(QMM_EUNSUPPORTED, "ADD + RMS_NORM: rows must be 16-byte aligned, ne0 %% 4 == 0 and ne0 <= 16384");
     const dim3 grid((unsigned) nrows(d));
+    QMM_TRACE(ctx, "rms_norm_kernel");
     if (w) hipLaunchKernelGGL((rms_norm_kernel<true>), grid, dim3(256), 0, st, (const char *) a->data, (const float *) w->data, (char *) d->data,
                               shape_of(a), shape_of(d), eps);
     else   hipLaunchKernelGGL((rms_norm_kernel<false>), grid, dim3(256), 0, st, (const char *) a->data, (const float *) nullptr, (char *) d->data,
@@ -2030,33 +2046,35 @@ int qmm_op_compute(qmm_ctx * ctx, int op, const qmm_tensor * a, const qmm_tensor
     QMM_CHAIN_FLUSH(ctx);
     hipStream_t st = ctx->s(stream);
     switch (op) {
-        case QMM_OP_ADD: return launch_binary<QMM_OP_ADD>(st, a, b, d);
-        case QMM_OP_SUB: return launch_binary<QMM_OP_SUB>(st, a, b, d);
-        case QMM_OP_MUL: return launch_binary<QMM_OP_MUL>(st, a, b, d);
-        case QMM_OP_DIV: return launch_binary<QMM_OP_DIV>(st, a, b, d);
-        case QMM_OP_SCALE:      return launch_unary<QMM_OP_SCALE, false>(st, a, nullptr, d, f32_param(d, 0));
-        case QMM_OP_SILU:       return launch_unary<QMM_OP_SILU, false>(st, a, nullptr, d, 0);
-        case QMM_OP_GELU:       return launch_unary<QMM_OP_GELU, false>(st, a, nullptr, d, 0);
-        case QMM_OP_GELU_QUICK: return launch_unary<QMM_OP_GELU_QUICK, false>(st, a, nullptr, d, 0);
-        case QMM_OP_RELU:       return launch_unary<QMM_OP_RELU, false>(st, a, nullptr, d, 0);
-        case QMM_OP_TANH:       return launch_unary<QMM_OP_TANH, false>(st, a, nullptr, d, 0);
-        case QMM_OP_SIGMOID:    return launch_unary<QMM_OP_SIGMOID, false>(st, a, nullptr, d, 0);
-        case QMM_OP_NEG:        return launch_unary<QMM_OP_NEG, false>(st, a, nullptr, d, 0);
-        case QMM_OP_EXP:        return launch_unary<QMM_OP_EXP, false>(st, a, nullptr, d, 0);
-        case QMM_OP_SILU_MUL:   return launch_unary<QMM_OP_SILU, true>(st, a, b, d, 0);
+        case QMM_OP_ADD: return launch_binary<QMM_OP_ADD>(ctx, st, a, b, d);
+        case QMM_OP_SUB: return launch_binary<QMM_OP_SUB>(ctx, st, a, b, d);
+        case QMM_OP_MUL: return launch_binary<QMM_OP_MUL>(ctx, st, a, b, d);
+        case QMM_OP_DIV: return launch_binary<QMM_OP_DIV>(ctx, st, a, b, d);
+        case QMM_OP_SCALE:      return launch_unary<QMM_OP_SCALE, false>(ctx, st, a, nullptr, d, f32_param(d, 0));
+        case QMM_OP_SILU:       return launch_unary<QMM_OP_SILU, false>(ctx, st, a, nullptr, d, 0);
+        case QMM_OP_GELU:       return launch_unary<QMM_OP_GELU, false>(ctx, st, a, nullptr, d, 0);
+        case QMM_OP_GELU_QUICK: return launch_unary<QMM_OP_GELU_QUICK, false>(ctx, st, a, nullptr, d, 0);
+        case QMM_OP_RELU:       return launch_unary<QMM_OP_RELU, false>(ctx, st, a, nullptr, d, 0);
+        case QMM_OP_TANH:       return launch_unary<QMM_OP_TANH, false>(ctx, st, a, nullptr, d, 0);
+        case QMM_OP_SIGMOID:    return launch_unary<QMM_OP_SIGMOID, false>(ctx, st, a, nullptr, d, 0);
+        case QMM_OP_NEG:        return launch_unary<QMM_OP_NEG, false>(ctx, st, a, nullptr, d, 0);
+        case QMM_OP_EXP:        return launch_unary<QMM_OP_EXP, false>(ctx, st, a, nullptr, d, 0);
+        case QMM_OP_SILU_MUL:   return launch_unary<QMM_OP_SILU, true>(ctx, st, a, b, d, 0);
         case QMM_OP_NORM: {
             const float eps = f32_param(d, 0);
             if (eps < 0.0f) return fail(QMM_EINVAL, "NORM: eps < 0");
+            QMM_TRACE(ctx, "norm_kernel");
             hipLaunchKernelGGL(norm_kernel, dim3((unsigned) nrows(d)), dim3(256), 0, st, (const char *) a->data, (char *) d->data, shape_of(a), shape_of(d), eps);
             HIP_TRY(hipGetLastError());
             return QMM_OK;
         }
         case QMM_OP_RMS_NORM:
         case QMM_OP_RMS_NORM_MUL:
-            return launch_rms_norm(st, a, nullptr, op == QMM_OP_RMS_NORM_MUL ? b : nullptr, d, nullptr, f32_param(d, 0));
+            return launch_rms_norm(ctx, st, a, nullptr, op == QMM_OP_RMS_NORM_MUL ? b : nullptr, d, nullptr, f32_param(d, 0));
         case QMM_OP_ROPE: {
             const RopeParams rp = rope_params(d);
             const uint32_t pairs = (uint32_t) (nelements(d) / 2);
+            QMM_TRACE(ctx, "rope_kernel");
             hipLaunchKernelGGL(rope_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, (const char *) a->data, (const int32_t *) b->data,
                                c ? (const float *) c->data : nullptr, (char *) d->data, shape_of(a), shape_of(d), rp, pairs);
             HIP_TRY(hipGetLastError());
@@ -2073,12 +2091,17 @@ int qmm_op_compute(qmm_ctx * ctx, int op, const qmm_tensor * a, const qmm_tensor
             if (max_bias == 0.0f && (!b || b->type == G_F32) && nc % 4 == 0 && nc <= 1024 && rows >= 1024 && (uintptr_t) a->data % 16 == 0 &&
                 (uintptr_t) d->data % 16 == 0 && (!b || (uintptr_t) b->data % 16 == 0)) {
                 const float * m = b ? (const float *) b->data : nullptr;
+                if (nc <= 256)      QMM_TRACE(ctx, "soft_max_wave_kernel<1>");
+                else if (nc <= 512) QMM_TRACE(ctx, "soft_max_wave_kernel<2>");
+                else                QMM_TRACE(ctx, "soft_max_wave_kernel<4>");
                 if (nc <= 256)      hipLaunchKernelGGL((soft_max_wave_kernel<1>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float *) a->data, m, (float *) d->data, nc, ne01, rows, scale);
                 else if (nc <= 512) hipLaunchKernelGGL((soft_max_wave_kernel<2>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float *) a->data, m, (float *) d->data, nc, ne01, rows, scale);
                 else                hipLaunchKernelGGL((soft_max_wave_kernel<4>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float *) a->data, m, (float *) d->data, nc, ne01, rows, scale);
                 HIP_TRY(hipGetLastError());
                 return QMM_OK;
             }
+            if (lds) QMM_TRACE(ctx, "soft_max_kernel<lds>");
+            else     QMM_TRACE(ctx, "soft_max_kernel<dst>");
             if (b && b->type == G_F16)
                 hipLaunchKernelGGL((soft_max_kernel<true>), grid, dim3(256), lds, st, (const float *) a->data, (const void *) b->data, (float *) d->data,
                                    nc, ne01, ne02, scale, max_bias, m0, m1, n_head_log2);
@@ -2088,16 +2111,17 @@ int qmm_op_compute(qmm_ctx * ctx, int op, const qmm_tensor * a, const qmm_tensor
             HIP_TRY(hipGetLastError());
             return QMM_OK;
         }
-        case QMM_OP_CPY: return launch_cpy(st, a, d);
+        case QMM_OP_CPY: return launch_cpy(ctx, st, a, d);
         case QMM_OP_GET_ROWS: {
             const dim3 grid((unsigned) nrows(d));
+            if (a->type == G_F32 || a->type == G_F16) QMM_TRACE(ctx, "get_rows_kernel");
             switch (a->type) {
                 case G_F32: hipLaunchKernelGGL((get_rows_kernel<float>), grid, dim3(256), 0, st, (const char *) a->data, (const char *) b->data,
                                                (char *) d->data, shape_of(a), shape_of(b), shape_of(d)); break;
                 case G_F16: hipLaunchKernelGGL((get_rows_kernel<__half>), grid, dim3(256), 0, st, (const char *) a->data, (const char *) b->data,
                                                (char *) d->data, shape_of(a), shape_of(b), shape_of(d)); break;
                 default: {
-#define QMM_X(TT) return launch_get_rows_q<TT>(st, a, b, d)
+#define QMM_X(TT) return launch_get_rows_q<TT>(ctx, st, a, b, d)
                     QMM_FOR_TYPE(a->type, QMM_X)
 #undef QMM_X
                 }
@@ -2105,14 +2129,16 @@ int qmm_op_compute(qmm_ctx * ctx, int op, const qmm_tensor * a, const qmm_tensor
             HIP_TRY(hipGetLastError());
             return QMM_OK;
         }
-        case QMM_OP_MUL_MAT_F: return launch_mul_mat_f(st, a, b, d);
+        case QMM_OP_MUL_MAT_F: return launch_mul_mat_f(ctx, st, a, b, d);
         case QMM_OP_ARGSORT:
+            QMM_TRACE(ctx, "argsort_kernel");
             hipLaunchKernelGGL(argsort_kernel, dim3((unsigned) nrows(a)), dim3(256), 0, st, (const char *) a->data, (char *) d->data, shape_of(a), shape_of(d),
                                d->op_params[0]);
             HIP_TRY(hipGetLastError());
             return QMM_OK;
         case QMM_OP_SUM_ROWS: {
             const uint32_t rows = (uint32_t) nrows(a);
+            QMM_TRACE(ctx, "sum_rows_kernel");
             hipLaunchKernelGGL(sum_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, (const char *) a->data, (char *) d->data, shape_of(a), shape_of(d), rows);
             HIP_TRY(hipGetLastError());
             return QMM_OK;
@@ -2126,7 +2152,7 @@ int qmm_op_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * a, const qmm_tensor * 
     if (!ctx || !qmm_op_add_rms_norm_supported(a, b, w, sum, dst)) return fail(QMM_EUNSUPPORTED, "qmm_op_add_rms_norm: operands not supported");
     HIP_TRY(hipSetDevice(ctx->device));
     QMM_CHAIN_FLUSH(ctx);
-    return launch_rms_norm(ctx->s(stream), a, b, w, dst, sum, eps);
+    return launch_rms_norm(ctx, ctx->s(stream), a, b, w, dst, sum, eps);
 }
 
 static bool attn_short_on() {                            // GGML_MI355X_ATTN_SHORT=0: the general kernel at every n_kv (A/B runs)

@@ -39,7 +39,7 @@ enum qmm_op {
     QMM_OP_ROPE,              /* src1 = positions (i32), src2 = frequency factors (f32) or NULL; op_params as ggml_rope_ext */
     QMM_OP_SOFT_MAX,          /* src1 = mask (f32 / f16) or NULL; op_params = {scale, max_bias} */
     QMM_OP_CPY,               /* also CONT and DUP: src0 -> dst, any strides, F32 / F16 either side */
-    QMM_OP_GET_ROWS,          /* src0 rows (F32 / F16 / the five quantized types) picked by src1 (i32) -> f32 */
+    QMM_OP_GET_ROWS,          /* src0 rows (F32 / F16 / every quantized weight type of ggml_mi355x_qmm.h) picked by src1 (i32) -> f32 */
     QMM_OP_MUL_MAT_F,         /* src0 F16 or F32 (any row strides, broadcast over dims 2/3), src1 F32 -> f32 */
     /* fused pairs the plugin forms from consecutive nodes */
     QMM_OP_RMS_NORM_MUL,      /* dst = rms_norm(src0) * src1, src1 one f32 row broadcast over all rows */

@@ -176,37 +176,41 @@ def test_add_rms_norm_two_results(qmm):
         assert rel_rms(y.cpu().numpy(), rms_norm(a + b, w, 1e-6)) < 2e-6
 
 
-def rope_ref(x, pos, n_dims, theta_scale):
-    """normal-mode rope of x [n_tok, n_head, d] with the CPU's repeated f32 multiply for theta (ggml-cpu.c:8634-8648)"""
-    out = x.copy()
-    for t in range(x.shape[0]):
-        theta = np.float32(pos[t])
-        for p in range(n_dims // 2):
-            c, s = np.float32(np.cos(np.float64(theta))), np.float32(np.sin(np.float64(theta)))
-            x0, x1 = x[t, :, 2 * p].copy(), x[t, :, 2 * p + 1].copy()
-            out[t, :, 2 * p] = x0 * c - x1 * s
-            out[t, :, 2 * p + 1] = x0 * s + x1 * c
-            theta = np.float32(theta * theta_scale)
-    return out
+def rope_ref(x, pos, n_dims, theta_scale=None, **kw):
+    """rope of x [n_tok, n_head, d] by the reference of tests/glue_refs.py (theta by the CPU's repeated f32 multiply, ggml-cpu.c:8634-8648;
+    cos / sin and the rotation in double), as float32; kw: neox, ff, the YaRN parameters"""
+    import glue_refs
+    return glue_refs.rope(x[None], pos, n_dims, **kw)[0].astype(np.float32)
 
 
-@pytest.mark.parametrize("n_tok", [1, 5, 70])
-def test_rope_kv_store_one_launch(qmm, n_tok):
-    """rope(q) -> f32, rope(k) -> f16 K cache rows, v -> transposed f16 V cache, as build_attn lays them out"""
+ROPE_STORE_CASES = [(1, "normal"), (5, "normal"), (70, "normal"), (5, "neox"), (70, "neox"), (5, "partial"), (5, "neox-partial"), (5, "ff"), (70, "neox-ff"),
+                    (5, "heads12"), (70, "neox-partial-ff-heads12")]
+
+
+@pytest.mark.parametrize("n_tok,variant", ROPE_STORE_CASES, ids=[str(n) if v == "normal" else f"{n}-{v}" for n, v in ROPE_STORE_CASES])
+def test_rope_kv_store_one_launch(qmm, n_tok, variant):
+    """rope(q) -> f32, rope(k) -> f16 K cache rows, v -> transposed f16 V cache, as build_attn lays them out; normal mode over the whole head,
+    NEOX, n_dims = 64 of d = 128 (pass-through channels), frequency factors, and 12 / 3 heads (a thread ropes up to ROPE_HC = 8 heads of one
+    pair: a chunk of 8 and a remainder of 4 for q, one short chunk for k)"""
     from ggml_hexagon_amd import capi
     rng = np.random.default_rng(7 + n_tok)
     d, h, hk, n_ctx, kv_head = 128, 8, 2, 96, 17
+    if "heads12" in variant:
+        h, hk = 12, 3
+    neox, n_dims = "neox" in variant, 64 if "partial" in variant else d
+    ffv = rng.uniform(0.8, 4.0, n_dims // 2).astype(np.float32) if "ff" in variant else None
     q = rng.normal(0, 1, (n_tok, h, d)).astype(np.float32)
     k = rng.normal(0, 1, (n_tok, hk, d)).astype(np.float32)
     v = rng.normal(0, 1, (n_tok, hk * d)).astype(np.float32)
     pos = np.arange(kv_head, kv_head + n_tok, dtype=np.int32)
     freq_base = 10000.0
-    theta_scale = np.float32(np.float32(freq_base) ** np.float32(-2.0 / d))
     dq, dk, dv, dpos = dev(q), dev(k), dev(v), dev(pos)
     q_out = torch.empty_like(dq)
     k_cache = torch.zeros((n_ctx, hk * d), dtype=torch.float16, device="cuda")
     v_cache = torch.zeros((hk * d, n_ctx), dtype=torch.float16, device="cuda")
-    params = [0, d, 0, 0, 8192, f2i(freq_base), f2i(1.0), f2i(0.0), f2i(1.0), f2i(32.0), f2i(1.0)]
+    params = [0, n_dims, 2 if neox else 0, 0, 8192, f2i(freq_base), f2i(1.0), f2i(0.0), f2i(1.0), f2i(32.0), f2i(1.0)]
+    dff = dev(ffv) if ffv is not None else None
+    tff = T(dff, F32, [n_dims // 2]) if ffv is not None else None
     tq = T(dq, F32, [d, h, n_tok])
     tqo = T(q_out, F32, [d, h, n_tok], op_params=params)
     tk = T(dk, F32, [d, hk, n_tok])
@@ -214,9 +218,11 @@ def test_rope_kv_store_one_launch(qmm, n_tok):
     tv = capi.QmmTensor.make(F32, [n_tok, hk * d], nb=[hk * d * 4, 4, 4 * n_tok * hk * d, 4 * n_tok * hk * d], data=dv.data_ptr())   # v_cur^T
     tvd = capi.QmmTensor.make(F16, [n_tok, hk * d], nb=[2, n_ctx * 2, n_ctx * 2 * hk * d, n_ctx * 2 * hk * d], data=v_cache.data_ptr() + kv_head * 2)
     r = lambda t: capi.C.byref(t)
-    qmm._chk(qmm.lib.qmm_rope_kv_store(qmm.ctx, r(tq), r(T(dpos, I32, [n_tok])), None, r(tqo), r(tk), r(tkd), r(tv), r(tvd), qmm._stream()))
-    want_q = rope_ref(q, pos, d, theta_scale)
-    want_k = rope_ref(k, pos, d, theta_scale).reshape(n_tok, hk * d).astype(np.float16)
+    tpos = T(dpos, I32, [n_tok])
+    assert qmm.lib.qmm_rope_kv_store_supported(r(tq), r(tpos), r(tff) if tff is not None else None, r(tqo), r(tk), r(tkd), r(tv), r(tvd)) == 1
+    qmm._chk(qmm.lib.qmm_rope_kv_store(qmm.ctx, r(tq), r(tpos), r(tff) if tff is not None else None, r(tqo), r(tk), r(tkd), r(tv), r(tvd), qmm._stream()))
+    want_q = rope_ref(q, pos, n_dims, neox=neox, ff=ffv)
+    want_k = rope_ref(k, pos, n_dims, neox=neox, ff=ffv).reshape(n_tok, hk * d).astype(np.float16)
     assert rel_rms(q_out.cpu().numpy(), want_q) < 2e-5
     kc = k_cache.cpu().numpy()
     assert np.max(np.abs(kc[kv_head:kv_head + n_tok].astype(np.float32) - want_k.astype(np.float32))) < 4e-3
@@ -226,7 +232,8 @@ def test_rope_kv_store_one_launch(qmm, n_tok):
     assert not vc[:, :kv_head].any() and not vc[:, kv_head + n_tok:].any()
 
 
-@pytest.mark.parametrize("n_tok,n_kv,d", [(1, 640, 128), (3, 96, 128), (1, 32, 64), (8, 1024, 128), (2, 4160, 128), (1, 1056, 64), (3, 16384, 128)])
+@pytest.mark.parametrize("n_tok,n_kv,d", [(1, 640, 128), (3, 96, 128), (1, 32, 64), (8, 1024, 128), (2, 4160, 128), (1, 1056, 64), (3, 16384, 128),
+                                           (1, 96, 256), (3, 640, 256), (2, 1056, 256)])
 def test_attn_decode_one_launch(qmm, n_tok, n_kv, d):
     """KQ -> soft_max(scale, mask) -> KQV -> merged heads, grouped-query, against f64 numpy with the CPU's f16 roundings of q and p"""
     from ggml_hexagon_amd import capi
