@@ -2,6 +2,9 @@
 // gfx950 only, no CPU path.  Every kernel is HBM-bound elementwise / row work except the small F16 attention matmuls,
 // which run on v_mfma_f32_32x32x16_f16.  Semantics follow the ggml CPU backend; each kernel cites the function it restates.
 // Parity: the reference's tests/test-backend-ops.cpp (built unmodified into oracle/_ref) against the CPU backend.
+// The attention launches (AttnArgs, AttnFresh, the five attn_* kernels, qmm_attn_decode / _decode_rope / _prefill and their
+// _supported predicates) are a section of their own, qmm_attn.hiph, included below behind qmm_rope_kv_store; what they launch
+// for a shape is decided by qmm_attn_plan.h.  The rope and MoE glue entry points stay here.
 
 #include "qmm_host.h"
 #include "../../include/ggml_mi355x_ops.h"
@@ -935,855 +938,6 @@ mul_mat_dot_kernel(const MmArgs g) {
     if (lane == 0) *(float *) (g.d + (int64_t) i12 * g.d_nb2 + (int64_t) i13 * g.d_nb3 + (int64_t) n * g.d_nb1 + (int64_t) m * 4) = s;
 }
 
-// ------------------------------------------------------------------------------------------------ attention, few tokens
-// The chain build_attn_mha emits without flash attention (src/llama-graph.cpp:1166-1203),
-//     kq = mul_mat(k, q);  p = soft_max_ext(kq, mask, scale);  kqv = mul_mat(v, p);  cont(permute(kqv, 0, 2, 1, 3))
-// for a batch of a few tokens (token generation) as ONE launch instead of four: a workgroup owns one (head, token), keeps the
-// n_kv scores in LDS and writes its head's slice of the merged output row.  Arithmetic as the CPU path has it: q and p are
-// rounded to f16 (vec_dot_type of an F16 src0 is F16, ggml-cpu.c type_traits_cpu), products accumulate in f32, the softmax
-// is the one of soft_max_kernel.  K rows are [D] f16 (dense), V is the transposed cache: row d holds n_kv f16.
-struct AttnArgs {
-    const char * q; const char * k; const char * v; const char * mask; char * dst;
-    int64_t q_nb1, q_nb2, k_nb1, k_nb2, v_nb1, v_nb2, m_nb1, d_nb1;
-    int32_t D, Dv, n_kv, H, gqa;
-    float   scale;
-};
-// 16 waves per workgroup and several independent loads in flight per lane: with one (head, token) per workgroup the kernel is
-// bound by load latency, not bandwidth (the first version, 4 waves and one row per lane group at a time, took 22 us at
-// n_kv = 640; the four separate launches it replaces took 16).
-// FRESH: the batch's own K / V rows are not in the cache yet — the launch also does what precedes the attention in build_attn
-// (src/llama-graph.cpp:1306-1365): rope(q), rope(k) -> K cache, v -> V cache.  q arrives un-roped; every workgroup ropes the N
-// new K rows of its kv head and converts the N new V rows into LDS and takes them from there for cache positions
-// j0 .. j0 + N (no workgroup reads those positions from memory, so the one workgroup per kv head that also stores them races
-// with nobody).  Normal-mode RoPE over the whole head (n_dims == D).
-struct AttnFresh {
-    const char * kraw; const char * vraw; char * kd; char * vd; const int32_t * pos; const float * ff;
-    int64_t kraw_nbh, kraw_nbn, vraw_nbn, kd_nbh, kd_nbn, vd_nbc;
-    RopeParams rp;
-    int32_t N, j0;
-};
-#ifdef ATTN_STAMPS                      // development builds only (profiles/tools/attn_dev.hip): 100 MHz stamps of workgroup phases
-__device__ unsigned long long attn_stamps[64][8];
-#define ATTN_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 64) attn_stamps[blockIdx.x][slot] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define ATTN_STAMP(slot) do { } while (0)
-#endif
-template <int D, bool FRESH>
-__global__ void __launch_bounds__(1024)
-attn_decode_kernel(const AttnArgs g, const AttnFresh f) {
-    extern __shared__ float sc[];                       // n_kv scores, then probabilities [FRESH: + q row f32, new K rows, new V rows f16]
-    __shared__ float red[16];
-    ATTN_STAMP(0);
-    // (all kernel arguments in one round trip: see attn_decode_short_kernel)
-    asm volatile("" :: "s"(g.q), "s"(g.k), "s"(g.v), "s"(g.mask), "s"(g.q_nb1), "s"(g.q_nb2), "s"(g.k_nb1), "s"(g.k_nb2), "s"(g.v_nb1), "s"(g.v_nb2), "s"(g.m_nb1),
-                 "s"(g.n_kv), "s"(g.gqa), "s"(g.Dv));
-    if (FRESH) asm volatile("" :: "s"(f.kraw), "s"(f.vraw), "s"(f.pos), "s"(f.ff), "s"(f.kraw_nbh), "s"(f.kraw_nbn), "s"(f.vraw_nbn), "s"(f.N));
-    const int h = blockIdx.x, n = blockIdx.y, hk = h / g.gqa;
-    const int tid = threadIdx.x, l8 = tid & 7, grp = tid >> 3;          // 128 groups of 8 lanes: one K row per group
-    constexpr int CH = D / 8;                           // halves of a K row per lane
-    constexpr int NV = CH / 8;                          // 16-byte loads per lane and row
-    float *    qs   = sc + g.n_kv;                      // FRESH only
-    _Float16 * knew = reinterpret_cast<_Float16 *>(qs + D);
-    _Float16 * vnew = knew + (FRESH ? f.N * D : 0);
-    const float * pm = (const float *) (g.mask + (int64_t) n * g.m_nb1);
-    const char *  pk = g.k + (int64_t) hk * g.k_nb2 + (int64_t) l8 * CH * 2;
-    // (measured and dropped: all of a group's K rows and all of a wave's V rows requested up front, 64 + 64 VGPRs: tg128 403 -> 395)
-    // two rows (jt, jt + 128) per trip, their loads issued together and one trip ahead of the arithmetic; the first trip is
-    // requested before anything else, so with FRESH the cache rows are already on their way while q / k / v are prepared
-    auto load_trip = [&](int jt, h16x8 (&kv)[2][NV], float (&mk)[2]) {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int j = jt + r * 128, jc = j < g.n_kv ? j : jt;
-            const h16x8 * row = (const h16x8 *) (pk + (int64_t) jc * g.k_nb1);
-#pragma unroll
-            for (int c = 0; c < NV; ++c) kv[r][c] = row[c];
-            mk[r] = pm[jc];
-        }
-    };
-    h16x8 kv[2][NV];
-    float mk[2];
-    if (grp < g.n_kv) load_trip(grp, kv, mk);
-    float qf[CH];
-    if (FRESH) {
-        const bool writer = h % g.gqa == 0 && n == 0;
-        for (int idx = tid; idx < f.N * (D / 2); idx += 1024) {
-            const int n2 = idx / (D / 2), p = idx % (D / 2);
-            const float * kr = (const float *) (f.kraw + (int64_t) hk * f.kraw_nbh + (int64_t) n2 * f.kraw_nbn);
-            float c, s;
-            rope_cs((float) f.pos[n2], (uint32_t) p, f.rp, f.ff, c, s);
-            const float x0 = kr[2 * p], x1 = kr[2 * p + 1];
-            const _Float16 y0 = (_Float16) (x0 * c - x1 * s), y1 = (_Float16) (x0 * s + x1 * c);
-            knew[n2 * D + 2 * p] = y0;
-            knew[n2 * D + 2 * p + 1] = y1;
-            if (writer) {
-                _Float16 * kd = reinterpret_cast<_Float16 *>(f.kd + (int64_t) hk * f.kd_nbh + (int64_t) n2 * f.kd_nbn);
-                kd[2 * p] = y0;
-                kd[2 * p + 1] = y1;
-            }
-        }
-        // the three preparations start on different waves (for one token: K on waves 0, V on waves 8-9, q on wave 4), so their
-        // load -> sincos -> store chains overlap instead of queueing on the same threads
-        for (int idx = (tid + 512) & 1023; idx < f.N * g.Dv; idx += 1024) {
-            const int n2 = idx / g.Dv, d = idx % g.Dv, ch = hk * g.Dv + d;
-            const _Float16 v = (_Float16) *(const float *) (f.vraw + (int64_t) ch * 4 + (int64_t) n2 * f.vraw_nbn);
-            vnew[n2 * g.Dv + d] = v;
-            if (writer) *reinterpret_cast<_Float16 *>(f.vd + (int64_t) n2 * 2 + (int64_t) ch * f.vd_nbc) = v;
-        }
-        if (const int t = tid - 256; t >= 0 && t < D / 2) {
-            const float * pq = (const float *) (g.q + (int64_t) n * g.q_nb1 + (int64_t) h * g.q_nb2);
-            float c, s;
-            rope_cs((float) f.pos[n], (uint32_t) t, f.rp, f.ff, c, s);
-            const float x0 = pq[2 * t], x1 = pq[2 * t + 1];
-            qs[2 * t] = x0 * c - x1 * s;
-            qs[2 * t + 1] = x0 * s + x1 * c;
-        }
-        ATTN_STAMP(1);
-        __syncthreads();
-        ATTN_STAMP(2);
-#pragma unroll
-        for (int e = 0; e < CH; ++e) qf[e] = (float) (_Float16) qs[l8 * CH + e];
-    } else {
-        const float * pq = (const float *) (g.q + (int64_t) n * g.q_nb1 + (int64_t) h * g.q_nb2) + l8 * CH;
-#pragma unroll
-        for (int e = 0; e < CH; ++e) qf[e] = (float) (_Float16) pq[e];
-    }
-    float mx = -INFINITY;
-    for (int jt = grp; jt < g.n_kv; jt += 256) {
-        h16x8 kvn[2][NV];
-        float mkn[2];
-        const bool more = jt + 256 < g.n_kv;
-        if (more) load_trip(jt + 256, kvn, mkn);
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int j = jt + r * 128;
-            if (FRESH && (unsigned) (j - f.j0) < (unsigned) f.N) {
-#pragma unroll
-                for (int c = 0; c < NV; ++c) kv[r][c] = *(const h16x8 *) &knew[(j - f.j0) * D + l8 * CH + c * 8];
-            }
-            float s = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NV; ++c)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) s += (float) kv[r][c][e] * qf[c * 8 + e];
-            s = sum8(s);
-            s = s * g.scale + mk[r];
-            if (j < g.n_kv) {
-                if (l8 == 0) sc[j] = s;
-                mx = fmaxf(mx, s);
-            }
-        }
-        if (more) {
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-#pragma unroll
-                for (int c = 0; c < NV; ++c) kv[r][c] = kvn[r][c];
-                mk[r] = mkn[r];
-            }
-        }
-    }
-    if (g.n_kv <= 512) {
-        // Short caches (token generation from an empty context: n_kv = 256): the kernel is a chain of latencies, not of bytes (12.9 us
-        // per layer for 64 KB of K and V), so the softmax is done by EVERY wave for itself from the scores in LDS: one barrier instead
-        // of seven, no block reductions, and the wave's eight V rows are requested together instead of in two trips.  A lane owns the
-        // eight columns it multiplies (j = 8 lane ...).  Same max, same exponentials; the sum runs in another order than below.
-        ATTN_STAMP(3);
-        __syncthreads();                                // sc[] complete
-        ATTN_STAMP(4);
-        const int lane = tid & 63, wave = tid >> 6;
-        const int jl = lane * 8;
-        const bool live = jl < g.n_kv;                  // (n_kv is a multiple of 8: qmm_attn_decode_supported)
-        const int jc = live ? jl : 0;
-        const char * pv = g.v + (int64_t) hk * g.v_nb2;
-        float * out = (float *) (g.dst + (int64_t) n * g.d_nb1) + (int64_t) h * g.Dv;
-        h16x8 vv[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {                   // rows wave + 16 r of the first 128; requested before the softmax arithmetic
-            const int d = wave + 16 * r < g.Dv ? wave + 16 * r : wave;
-            vv[r] = *(const h16x8 *) (pv + (int64_t) d * g.v_nb1 + (int64_t) jc * 2);
-        }
-        float sv[8], m = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { sv[e] = live ? sc[jl + e] : -INFINITY; m = fmaxf(m, sv[e]); }
-        m = wave_max(m);
-        float sum = 0.0f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { sv[e] = live ? expf(sv[e] - m) : 0.0f; sum += sv[e]; }
-        sum = wave_sum(sum);
-        const float inv = 1.0f / sum;
-        float pr[8], pfresh[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pr[e] = (float) (_Float16) (sv[e] * inv);
-        ATTN_STAMP(5);
-        if (FRESH) {                                    // the batch's own positions: probability set aside, column weight 0 (see below)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                pfresh[i] = i < f.N ? (float) (_Float16) (expf(sc[f.j0 + i] - m) * inv) : 0.0f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) if (i < f.N && jl + e == f.j0 + i) pr[e] = 0.0f;
-            }
-        }
-        for (int d0 = wave; d0 < g.Dv; d0 += 128) {
-            if (d0 != wave) {
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int d = d0 + 16 * r < g.Dv ? d0 + 16 * r : d0;
-                    vv[r] = *(const h16x8 *) (pv + (int64_t) d * g.v_nb1 + (int64_t) jc * 2);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc += (float) vv[r][e] * pr[e];
-                float t = wave_sum(acc);
-                const int d = d0 + 16 * r;
-                if (lane == 0 && d < g.Dv) {
-                    if (FRESH) {
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) if (i < f.N) t += pfresh[i] * (float) vnew[i * g.Dv + d];
-                    }
-                    out[d] = t;
-                }
-            }
-        }
-        ATTN_STAMP(6);
-        return;
-    }
-    mx = block_reduce<true>(mx, red);                   // its barriers also publish sc[]
-    float sum = 0.0f;
-    for (int j = tid; j < g.n_kv; j += 1024) {
-        const float e = expf(sc[j] - mx);
-        sc[j] = e;
-        sum += e;
-    }
-    sum = block_reduce<false>(sum, red);
-    const float inv = 1.0f / sum;
-    for (int j = tid; j < g.n_kv; j += 1024) sc[j] = (float) (_Float16) (sc[j] * inv);
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6;
-    float * out = (float *) (g.dst + (int64_t) n * g.d_nb1) + (int64_t) h * g.Dv;
-    const char * pv = g.v + (int64_t) hk * g.v_nb2;
-    // FRESH: the probabilities of the batch's own positions are set aside and zeroed in sc[], so the main loop runs over the
-    // (stale, finite) cache values of those columns with weight 0 and the new V rows come in as a rank-N update at the end
-    float pfresh[8];
-    if (FRESH) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) pfresh[i] = i < f.N ? sc[f.j0 + i] : 0.0f;
-        __syncthreads();
-        if (tid < f.N) sc[f.j0 + tid] = 0.0f;
-        __syncthreads();
-    }
-    for (int d0 = wave; d0 < g.Dv; d0 += 64) {          // four V rows (d0, +16, +32, +48) per trip
-        float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-        for (int j = lane * 8; j < g.n_kv; j += 1024) {   // two column blocks (j, j + 512) per pass: eight loads requested together
-            h16x8 vv[2][4];
-            const int j2 = j + 512 < g.n_kv ? j + 512 : j;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int d = d0 + 16 * r < g.Dv ? d0 + 16 * r : d0;
-                vv[0][r] = *(const h16x8 *) (pv + (int64_t) d * g.v_nb1 + (int64_t) j * 2);
-                vv[1][r] = *(const h16x8 *) (pv + (int64_t) d * g.v_nb1 + (int64_t) j2 * 2);
-            }
-            float p[2][8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { p[0][e] = sc[j + e]; p[1][e] = j + 512 < g.n_kv ? sc[j2 + e] : 0.0f; }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[r] += (float) vv[0][r][e] * p[0][e] + (float) vv[1][r][e] * p[1][e];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float t = wave_sum(acc[r]);
-            const int d = d0 + 16 * r;
-            if (lane == 0 && d < g.Dv) {
-                if (FRESH) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) if (i < f.N) t += pfresh[i] * (float) vnew[i * g.Dv + d];
-                }
-                out[d] = t;
-            }
-        }
-    }
-}
-
-// Short caches (n_kv <= 1024 in one or two halves of 512 columns, D and Dv <= 128: token generation inside llama.cpp's first windows, where the launch is a chain of
-// latencies: 64 KB of K and V per head).  Round 3 stamps of the kernel above at n_kv = 256 (profiles/tools/attn_dev.hip): 2.9 us until
-// the new rows are roped and in LDS, 0.9 us scores, 0.8 us softmax, 2.6 us for the V product (its loads requested behind the second
-// barrier), 7.9 us in the kernel for a 10.5 us slot.  This one
-//   * requests EVERYTHING at entry: the thread's share of the new q / k / v values first, then its four K rows, masks and its
-//     eight V rows (the V loads were 1.5 us of exposed latency behind the softmax), and only then starts to compute;
-//   * spreads the preparation of one token over waves 0-3, one per SIMD (q pairs, K pairs, V values; they were waves 0, 4 and 8:
-//     the same SIMD);
-//   * takes one exponential per column (thread j, through LDS) instead of eight per lane in every wave;
-//   * multiplies f16 x f16 into f32 directly (v_fma_mix: the products of the conversions, exactly as before);
-//   * folds the eight V-row sums of a wave into one register with v_permlane32_swap / v_permlane16_swap before the DPP steps
-//     (20 instructions instead of 8 wave_sums).
-// Same arithmetic as the CPU chain (q, p rounded to f16, f32 accumulation, soft_max_kernel's max / exp / sum); sums in another order.
-template <int D, bool FRESH, int WIDTH>
-__global__ void __launch_bounds__(1024)
-attn_decode_short_kernel(const AttnArgs g, const AttnFresh f) {
-    extern __shared__ float sc[];       // n_kv scores | n_kv exponentials [FRESH: | q row f16 (D halves, D floats reserved) | new K rows f16 | new V rows f16]
-    ATTN_STAMP(0);
-    // every kernel argument the address arithmetic below needs is requested HERE, in one round trip: left to itself hipcc issues the
-    // s_loads where the values are first used, three dependent waits (1.2 us from entry to the first global load, stamped)
-    asm volatile("" :: "s"(g.q), "s"(g.k), "s"(g.v), "s"(g.mask), "s"(g.q_nb1), "s"(g.q_nb2), "s"(g.k_nb1), "s"(g.k_nb2), "s"(g.v_nb1), "s"(g.v_nb2), "s"(g.m_nb1),
-                 "s"(g.n_kv), "s"(g.gqa), "s"(g.Dv));
-    if (FRESH) asm volatile("" :: "s"(f.kraw), "s"(f.vraw), "s"(f.pos), "s"(f.ff), "s"(f.kraw_nbh), "s"(f.kraw_nbn), "s"(f.vraw_nbn), "s"(f.N));
-    const int h = blockIdx.x, n = blockIdx.y, hk = h / g.gqa;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l8 = tid & 7, grp = tid >> 3;
-    constexpr int CH = D / 8, NV = CH / 8, HP = D / 2;
-    static_assert(WIDTH == 256 || WIDTH == 512 || WIDTH == 1024, "cache columns this instantiation covers");
-    constexpr int NR = WIDTH == 256 ? 2 : 4;            // K rows per 8-lane group and trip (n_kv <= 256: two)
-    constexpr int CPL = WIDTH == 256 ? 4 : 8;           // cache columns per lane and trip in the softmax and the V product
-    constexpr int TRIPS = WIDTH == 1024 ? 2 : 1;        // n_kv <= 1024: the cache in two halves of 512 columns through the same registers
-    typedef _Float16 hcol __attribute__((ext_vector_type(CPL)));
-    float *    ex   = sc + g.n_kv;
-    _Float16 * qs   = reinterpret_cast<_Float16 *>(ex + g.n_kv);
-    _Float16 * knew = qs + 2 * D;
-    _Float16 * vnew = knew + (FRESH ? f.N * D : 0);
-    // ---- requests.  FRESH: item `it` of the batch's preparation: q pairs [0, HP), K pairs (HP per token), then V values
-    const int nk = FRESH ? f.N * HP : 0, items = FRESH ? HP + nk + f.N * g.Dv : 0;
-    auto item = [&](int it, const float *& p0, const float *& p1, int & tok) {
-        if (it < HP) {
-            const float * pq = (const float *) (g.q + (int64_t) n * g.q_nb1 + (int64_t) h * g.q_nb2);
-            p0 = pq + 2 * it; p1 = p0 + 1; tok = n;
-        } else if (it < HP + nk) {
-            const int n2 = (it - HP) / HP, p = (it - HP) % HP;
-            const float * kr = (const float *) (f.kraw + (int64_t) hk * f.kraw_nbh + (int64_t) n2 * f.kraw_nbn);
-            p0 = kr + 2 * p; p1 = p0 + 1; tok = n2;
-        } else {
-            const int n2 = (it - HP - nk) / g.Dv, d = (it - HP - nk) % g.Dv;
-            p0 = p1 = (const float *) (f.vraw + (int64_t) (hk * g.Dv + d) * 4 + (int64_t) n2 * f.vraw_nbn); tok = n2;
-        }
-    };
-    float x0 = 0.0f, x1 = 0.0f, xff = 1.0f;
-    int32_t xpos = 0;
-    if (FRESH) {
-        const float * p0, * p1; int tok;
-        const int it0 = tid < items ? tid : 0;
-        item(it0, p0, p1, tok);
-        const float * pf = f.ff ? f.ff + (it0 < HP ? it0 : it0 < HP + nk ? (it0 - HP) % HP : 0) : p0;     // the pair's frequency factor
-        // asm: as C++ loads hipcc sinks these four into the branches that use them, BEHIND the cache loads below (vmcnt retires in
-        // order), and as volatile loads it waits for each.  The wait that releases them counts the cache loads: see below
-        const int32_t * pp = f.pos + tok;
-        asm volatile("global_load_dword %0, %4, off\n\tglobal_load_dword %1, %5, off\n\tglobal_load_dword %2, %6, off\n\tglobal_load_dword %3, %7, off"
-                     : "=&v"(xpos), "=&v"(x0), "=&v"(x1), "=&v"(xff) : "v"(pp), "v"(p0), "v"(p1), "v"(pf) : "memory");
-    }
-    h16x8 kv[NR][NV];
-    float mk[NR];
-    {
-        const float * pm = (const float *) (g.mask + (int64_t) n * g.m_nb1);
-        const char *  pk = g.k + (int64_t) hk * g.k_nb2 + (int64_t) l8 * CH * 2;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const int j = grp + 128 * r, jc = j < g.n_kv ? j : g.n_kv - 1;
-            const h16x8 * row = (const h16x8 *) (pk + (int64_t) jc * g.k_nb1);
-#pragma unroll
-            for (int c = 0; c < NV; ++c) kv[r][c] = row[c];
-            mk[r] = pm[jc];
-        }
-    }
-    const int jl = lane * CPL;
-    const bool live = jl < g.n_kv;                      // (n_kv is a multiple of 8: qmm_attn_decode_supported)
-    hcol vv[8];
-    {
-        const char * pv = g.v + (int64_t) hk * g.v_nb2 + (int64_t) (live ? jl : 0) * 2;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {                   // rows wave + 16 r
-            const int d = wave + 16 * r < g.Dv ? wave + 16 * r : 0;
-            vv[r] = *(const hcol *) (pv + (int64_t) d * g.v_nb1);
-        }
-    }
-    _Float16 qh[CH];
-    if (!FRESH) {
-        const float * pq = (const float *) (g.q + (int64_t) n * g.q_nb1 + (int64_t) h * g.q_nb2) + l8 * CH;
-#pragma unroll
-        for (int e = 0; e < CH; ++e) qh[e] = (_Float16) pq[e];
-    }
-    ATTN_STAMP(7);
-    // ---- the batch's own rows: rope(q) -> LDS, rope(k) -> LDS and K cache, v -> LDS and V cache
-    if (FRESH) {
-        constexpr int BEHIND = NR * NV + NR + 8;        // K rows, masks and V rows requested behind the four asm loads
-        static_assert(BEHIND == 20 || BEHIND == 16 || BEHIND == 14 || BEHIND == 12, "vmcnt immediates below");
-        if (BEHIND == 20)      asm volatile("s_waitcnt vmcnt(20)" : "+v"(xpos), "+v"(x0), "+v"(x1), "+v"(xff) :: "memory");
-        else if (BEHIND == 16) asm volatile("s_waitcnt vmcnt(16)" : "+v"(xpos), "+v"(x0), "+v"(x1), "+v"(xff) :: "memory");
-        else if (BEHIND == 14) asm volatile("s_waitcnt vmcnt(14)" : "+v"(xpos), "+v"(x0), "+v"(x1), "+v"(xff) :: "memory");
-        else                   asm volatile("s_waitcnt vmcnt(12)" : "+v"(xpos), "+v"(x0), "+v"(x1), "+v"(xff) :: "memory");
-        if (!f.ff) xff = 1.0f;
-        const bool writer = h % g.gqa == 0 && n == 0;
-        auto prepare = [&](int it, float a, float b, float posf, float ffp) {
-            if (it < HP + nk) {
-                const int p = it < HP ? it : (it - HP) % HP;
-                float c, s;
-                rope_cs_ff(posf, (uint32_t) p, f.rp, ffp, c, s);
-                const _Float16 h0 = (_Float16) (a * c - b * s), h1 = (_Float16) (a * s + b * c);
-                if (it < HP) { qs[2 * p] = h0; qs[2 * p + 1] = h1; }        // (q is rounded to f16 by the product with K anyway)
-                else {
-                    const int n2 = (it - HP) / HP;
-                    knew[n2 * D + 2 * p] = h0; knew[n2 * D + 2 * p + 1] = h1;
-                    if (writer) {
-                        _Float16 * kd = reinterpret_cast<_Float16 *>(f.kd + (int64_t) hk * f.kd_nbh + (int64_t) n2 * f.kd_nbn);
-                        kd[2 * p] = h0; kd[2 * p + 1] = h1;
-                    }
-                }
-            } else {
-                const int n2 = (it - HP - nk) / g.Dv, d = (it - HP - nk) % g.Dv;
-                const _Float16 v = (_Float16) a;
-                vnew[n2 * g.Dv + d] = v;
-                if (writer) *reinterpret_cast<_Float16 *>(f.vd + (int64_t) n2 * 2 + (int64_t) (hk * g.Dv + d) * f.vd_nbc) = v;
-            }
-        };
-        if (wave * 64 < items) {                        // wave-uniform: the other waves go straight to the barrier
-            if (tid < items) prepare(tid, x0, x1, (float) xpos, xff);
-            for (int it = tid + 1024; it < items; it += 1024) {     // batches of several tokens
-                const float * p0, * p1; int tok;
-                item(it, p0, p1, tok);
-                prepare(it, *p0, *p1, (float) f.pos[tok], f.ff && it < HP + nk ? f.ff[it < HP ? it : (it - HP) % HP] : 1.0f);
-            }
-        }
-        ATTN_STAMP(1);
-        __syncthreads();
-        ATTN_STAMP(2);
-#pragma unroll
-        for (int c = 0; c < NV; ++c) {
-            const h16x8 t = *(const h16x8 *) &qs[l8 * CH + c * 8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qh[c * 8 + e] = t[e];
-        }
-    }
-    // ---- scores
-#pragma unroll
-    for (int trip = 0; trip < TRIPS; ++trip) {
-        if (trip > 0) {                                 // the second half's rows into the registers the first half has released
-            const float * pm = (const float *) (g.mask + (int64_t) n * g.m_nb1);
-            const char *  pk = g.k + (int64_t) hk * g.k_nb2 + (int64_t) l8 * CH * 2;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                const int j = 512 * trip + grp + 128 * r, jc = j < g.n_kv ? j : g.n_kv - 1;
-                const h16x8 * row = (const h16x8 *) (pk + (int64_t) jc * g.k_nb1);
-#pragma unroll
-                for (int c = 0; c < NV; ++c) kv[r][c] = row[c];
-                mk[r] = pm[jc];
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const int j = 512 * trip + grp + 128 * r;
-            if (FRESH && (unsigned) (j - f.j0) < (unsigned) f.N) {
-#pragma unroll
-                for (int c = 0; c < NV; ++c) kv[r][c] = *(const h16x8 *) &knew[(j - f.j0) * D + l8 * CH + c * 8];
-            }
-            float s = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NV; ++c)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) s += (float) kv[r][c][e] * (float) qh[c * 8 + e];
-            s = sum8(s);
-            s = s * g.scale + mk[r];
-            if (j < g.n_kv && l8 == 0) sc[j] = s;
-        }
-    }
-    // the second half's V rows are requested here (the K rows' registers are free), in front of the softmax arithmetic
-    hcol vv2[8];
-    const int jl2 = 512 + jl;
-    const bool live2 = TRIPS > 1 && jl2 < g.n_kv;
-    if (TRIPS > 1) {
-        const char * pv = g.v + (int64_t) hk * g.v_nb2 + (int64_t) (live2 ? jl2 : 0) * 2;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const int d = wave + 16 * r < g.Dv ? wave + 16 * r : 0;
-            vv2[r] = *(const hcol *) (pv + (int64_t) d * g.v_nb1);
-        }
-    }
-    ATTN_STAMP(3);
-    __syncthreads();
-    ATTN_STAMP(4);
-    // ---- softmax: every wave takes the maximum for itself, thread j the exponential of column j
-    float m = -INFINITY;
-#pragma unroll
-    for (int trip = 0; trip < TRIPS; ++trip) {
-        const int jt = 512 * trip + jl;
-#pragma unroll
-        for (int e = 0; e < CPL; e += 4) {
-            const float4 a = jt < g.n_kv ? *(const float4 *) &sc[jt + e] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-            m = fmaxf(m, fmaxf(fmaxf(a.x, a.y), fmaxf(a.z, a.w)));
-        }
-    }
-    m = wave_max(m);
-    if (tid < g.n_kv) ex[tid] = expf(sc[tid] - m);
-    __syncthreads();
-    float e8[TRIPS][CPL];
-    float sum = 0.0f;
-#pragma unroll
-    for (int trip = 0; trip < TRIPS; ++trip) {
-        const int jt = 512 * trip + jl;
-#pragma unroll
-        for (int e = 0; e < CPL; e += 4) {
-            const float4 a = jt < g.n_kv ? *(const float4 *) &ex[jt + e] : make_float4(0.f, 0.f, 0.f, 0.f);
-            e8[trip][e] = a.x; e8[trip][e + 1] = a.y; e8[trip][e + 2] = a.z; e8[trip][e + 3] = a.w;
-        }
-#pragma unroll
-        for (int e = 0; e < CPL; ++e) sum += e8[trip][e];
-    }
-    sum = wave_sum(sum);
-    const float inv = 1.0f / sum;
-    _Float16 pr[TRIPS][CPL];
-#pragma unroll
-    for (int trip = 0; trip < TRIPS; ++trip)
-#pragma unroll
-        for (int e = 0; e < CPL; ++e) {                 // the batch's own positions: column weight 0, their rows come from LDS below
-            const bool fresh = FRESH && (unsigned) (512 * trip + jl + e - f.j0) < (unsigned) f.N;
-            pr[trip][e] = fresh ? (_Float16) 0.0f : (_Float16) (e8[trip][e] * inv);
-        }
-    ATTN_STAMP(5);
-    // ---- V product: eight rows per wave, their 64 partial sums each folded pairwise into one register
-    float acc[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        acc[r] = 0.0f;
-#pragma unroll
-        for (int e = 0; e < CPL; ++e) acc[r] += (float) vv[r][e] * (float) pr[0][e];
-        if (TRIPS > 1) {
-#pragma unroll
-            for (int e = 0; e < CPL; ++e) acc[r] += (float) vv2[r][e] * (float) pr[TRIPS - 1][e];
-        }
-    }
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    float t4[4], t2[2];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {                       // lanes 0-31: row r, lanes 32-63: row r + 4
-        const u32x2 w = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[r]), __float_as_uint(acc[r + 4]), false, false);
-        t4[r] = __uint_as_float(w.x) + __uint_as_float(w.y);
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {                       // 16-lane rows: r, r + 2, r + 4, r + 6
-        const u32x2 w = __builtin_amdgcn_permlane16_swap(__float_as_uint(t4[r]), __float_as_uint(t4[r + 2]), false, false);
-        t2[r] = __uint_as_float(w.x) + __uint_as_float(w.y);
-    }
-    t2[0] += dpp_mov<DPP_ROW_MIRROR>(t2[0]);
-    t2[1] += dpp_mov<DPP_ROW_MIRROR>(t2[1]);
-    float t = sum8(lane & 8 ? t2[1] : t2[0]);           // lanes 16 R + 8 b ...: row 2 R + b
-    const int d = wave + 16 * (2 * (lane >> 4) + ((lane >> 3) & 1));
-    if (l8 == 0 && d < g.Dv) {
-        if (FRESH)
-            for (int i = 0; i < f.N; ++i) t += (float) (_Float16) (ex[f.j0 + i] * inv) * (float) vnew[i * g.Dv + d];
-        ((float *) (g.dst + (int64_t) n * g.d_nb1) + (int64_t) h * g.Dv)[d] = t;
-    }
-    ATTN_STAMP(6);
-}
-
-// Long caches at batch <= 8: one workgroup per (head, token) walks the whole cache (45 us per layer at n_kv = 4160).  From
-// n_kv = 1024 the kv range is cut into S pieces, one workgroup each (grid z), which leave (max, sum, unnormalised output row) in
-// the workspace; attn_combine_kernel merges them with the usual rescaling.  p stays f32 here (the single-workgroup kernel and
-// the CPU round the normalised p to f16 before the product with V): results agree to ~2^-11 relative.
-template <int D>
-__global__ void __launch_bounds__(1024)
-attn_decode_split_kernel(const AttnArgs g, float * __restrict__ part, const int S, const int chunk) {
-    extern __shared__ float sc[];                       // this piece's scores, then exp(score - max)
-    __shared__ float red[16];
-    const int h = blockIdx.x, n = blockIdx.y, sp = blockIdx.z, hk = h / g.gqa;
-    const int j_lo = sp * chunk, j_hi = min(g.n_kv, j_lo + chunk), len = max(j_hi - j_lo, 0);
-    const int tid = threadIdx.x, l8 = tid & 7, grp = tid >> 3;
-    constexpr int CH = D / 8, NV = CH / 8;
-    float qf[CH];
-    {
-        const float * pq = (const float *) (g.q + (int64_t) n * g.q_nb1 + (int64_t) h * g.q_nb2) + l8 * CH;
-#pragma unroll
-        for (int e = 0; e < CH; ++e) qf[e] = (float) (_Float16) pq[e];
-    }
-    const float * pm = (const float *) (g.mask + (int64_t) n * g.m_nb1);
-    const char *  pk = g.k + (int64_t) hk * g.k_nb2 + (int64_t) l8 * CH * 2;
-    float mx = -INFINITY;
-    for (int jt = j_lo + grp; jt < j_hi; jt += 256) {
-        h16x8 kv[2][NV];
-        float mk[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int j = jt + r * 128, jc = j < j_hi ? j : jt;
-            const h16x8 * row = (const h16x8 *) (pk + (int64_t) jc * g.k_nb1);
-#pragma unroll
-            for (int c = 0; c < NV; ++c) kv[r][c] = row[c];
-            mk[r] = pm[jc];
-        }
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int j = jt + r * 128;
-            float s = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NV; ++c)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) s += (float) kv[r][c][e] * qf[c * 8 + e];
-            s = sum8(s);
-            s = s * g.scale + mk[r];
-            if (j < j_hi) {
-                if (l8 == 0) sc[j - j_lo] = s;
-                mx = fmaxf(mx, s);
-            }
-        }
-    }
-    mx = block_reduce<true>(mx, red);
-    float sum = 0.0f;
-    for (int j = tid; j < len; j += 1024) {
-        const float e = mx == -INFINITY ? 0.0f : expf(sc[j] - mx);
-        sc[j] = e;
-        sum += e;
-    }
-    sum = block_reduce<false>(sum, red);                // its barriers publish sc[]
-    const int lane = tid & 63, wave = tid >> 6;
-    float * po = part + ((int64_t) (h * gridDim.y + n) * S + sp) * (g.Dv + 2);
-    if (tid == 0) { po[0] = mx; po[1] = sum; }
-    const char * pv = g.v + (int64_t) hk * g.v_nb2;
-    for (int d0 = wave; d0 < g.Dv; d0 += 64) {
-        float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-        for (int j = lane * 8; j < len; j += 512) {
-            h16x8 vv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int d = d0 + 16 * r < g.Dv ? d0 + 16 * r : d0;
-                vv[r] = *(const h16x8 *) (pv + (int64_t) d * g.v_nb1 + (int64_t) (j_lo + j) * 2);
-            }
-            float p[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) p[e] = j + e < len ? sc[j + e] : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[r] += (float) vv[r][e] * p[e];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float t = wave_sum(acc[r]);
-            if (lane == 0 && d0 + 16 * r < g.Dv) po[2 + d0 + 16 * r] = t;
-        }
-    }
-}
-__global__ void __launch_bounds__(256)
-attn_combine_kernel(const float * __restrict__ part, char * __restrict__ dst, const int64_t d_nb1, const int Dv, const int S) {
-    const int h = blockIdx.x, n = blockIdx.y;
-    const float * pp = part + (int64_t) (h * gridDim.y + n) * S * (Dv + 2);
-    float M = -INFINITY;
-    for (int s = 0; s < S; ++s) M = fmaxf(M, pp[(int64_t) s * (Dv + 2)]);
-    float L = 0.0f;
-    for (int s = 0; s < S; ++s) L += pp[(int64_t) s * (Dv + 2) + 1] * expf(pp[(int64_t) s * (Dv + 2)] - M);
-    float * out = (float *) (dst + (int64_t) n * d_nb1) + (int64_t) h * Dv;
-    for (int d = threadIdx.x; d < Dv; d += 256) {
-        float o = 0.0f;
-        for (int s = 0; s < S; ++s) o += pp[(int64_t) s * (Dv + 2) + 2 + d] * expf(pp[(int64_t) s * (Dv + 2)] - M);
-        out[d] = o / L;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ attention, prompt batches
-// The same chain for a prompt batch whose scores fit LDS (n_kv <= 512: llama-bench's pp512), one workgroup of 4 waves per
-// (64 tokens, head).  The three-launch form is bound by the f32 score tensor (33 MB per layer at 512 x 512 x 32: written by KQ,
-// read and written by soft_max, read by KQV); here the 64 x n_kv scores live in LDS from the first MFMA to the last:
-//   1. S = scale * Q K^T + mask      K tiles of 64 rows through LDS, Q fragments in registers, v_mfma_f32_32x32x16_f16
-//   2. soft_max per row in LDS       a wave per row, the row in registers; p is stored back as f16 in the row's own bytes
-//   3. O = P V                       V^T tiles of 32 columns through LDS, P fragments read from the score rows
-// q and p are rounded to f16 as on the CPU path (F16 vec_dot); the result goes out in the merged-heads layout.
-constexpr int AP_TN = 64, AP_KT = 64, AP_CH = 512;                        // tokens per workgroup, K rows / V columns per tile, kv columns per chunk
-// Caches longer than one chunk are walked chunk by chunk with the usual running (max, sum) per token row: the output accumulators
-// are rescaled by exp(max_old - max_new) before a chunk's P V is added and divided by the sum at the end.  With several chunks
-// p is stored unnormalised (exp(s - max), f16): against the CPU, which rounds the normalised p, results agree to f16 rounding
-// (~1e-3 of an output at worst); a cache of one chunk keeps the CPU's order of operations.
-template <int D>
-__global__ void __launch_bounds__(256)
-attn_prefill_kernel(const AttnArgs g, const int N) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t ap_smem[];
-    __shared__ int tile_dead[AP_CH / AP_KT];                               // kv tile fully masked for all 64 tokens (the causal upper triangle)
-    __shared__ float row_max[AP_TN], row_sum[AP_TN], row_alpha[AP_TN];
-    const int CW = g.n_kv < AP_CH ? g.n_kv : AP_CH;                        // chunk width
-    const bool single = g.n_kv <= AP_CH;
-    const int SP = CW + 4;                                                 // score row pitch in floats: 16-byte reads of 32 rows hit distinct banks
-    float *    S  = reinterpret_cast<float *>(ap_smem);
-    _Float16 * tl = reinterpret_cast<_Float16 *>(ap_smem + (size_t) AP_TN * SP * 4);      // K tile [64][D + 8], later V tile [D][64 + 8]
-    constexpr int KP = D + 8, VP = AP_KT + 8;
-    constexpr int NCH = AP_KT * D / 8 / 256;                               // 16-byte chunks of a tile per thread (both tiles hold 64 * D halves)
-    const int h = blockIdx.y, hk = h / g.gqa, n0 = blockIdx.x * AP_TN;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, hh = lane >> 5;
-    const int tw = wave & 1, kw = wave >> 1;
-
-    // Q fragments of this wave's 32 tokens (MFMA rows), f32 -> f16
-    h16x8 qf[D / 16];
-    {
-        const int n = n0 + 32 * tw + l32;
-        const float * pq = (const float *) (g.q + (int64_t) (n < N ? n : N - 1) * g.q_nb1 + (int64_t) h * g.q_nb2);
-#pragma unroll
-        for (int kk = 0; kk < D / 16; ++kk) {
-            const float4 x = *(const float4 *) (pq + 16 * kk + 8 * hh), y = *(const float4 *) (pq + 16 * kk + 8 * hh + 4);
-            qf[kk] = h16x8{ (_Float16) x.x, (_Float16) x.y, (_Float16) x.z, (_Float16) x.w, (_Float16) y.x, (_Float16) y.y, (_Float16) y.z, (_Float16) y.w };
-        }
-    }
-    if (tid < AP_TN) { row_max[tid] = -INFINITY; row_sum[tid] = 0.0f; }
-    constexpr int DT = D / 64;                                             // 32-wide d tiles per wave
-    constexpr int CPR = D / 8;                                             // 16-byte chunks per K row
-    constexpr int VPR = AP_KT / 8;                                         // 16-byte chunks per V^T row of the tile
-    f32x16v oacc[DT];
-#pragma unroll
-    for (int t = 0; t < DT; ++t) oacc[t] = f32x16v{0};
-    const char * pk = g.k + (int64_t) hk * g.k_nb2;
-    const char * pv = g.v + (int64_t) hk * g.v_nb2;
-    h16x8 pre[NCH];
-
-    for (int c0 = 0; c0 < g.n_kv; c0 += AP_CH) {
-        const int c1 = c0 + AP_CH < g.n_kv ? c0 + AP_CH : g.n_kv;          // this chunk: kv columns c0 .. c1
-        // 1. scores.  A tile's K rows are requested one tile ahead, so the loads fly under the MFMAs of the current one.
-        auto fetch_k = [&](int j0) {
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                const int c = tid + 256 * i, row = c / CPR, col = c % CPR;
-                pre[i] = h16x8{0};
-                if (j0 + row < c1) pre[i] = *(const h16x8 *) (pk + (int64_t) (j0 + row) * g.k_nb1 + col * 16);
-            }
-        };
-        fetch_k(c0);
-        int live_tiles = 0;
-        for (int j0 = c0, jt = 0; j0 < c1; j0 += AP_KT, ++jt) {
-            const int j = j0 + 32 * kw + l32;
-            float m[16];
-            int dead = 1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int n = n0 + 32 * tw + 8 * (r >> 2) + 4 * hh + (r & 3);
-                m[r] = j < c1 ? *(const float *) (g.mask + (int64_t) (n < N ? n : N - 1) * g.m_nb1 + (int64_t) j * 4) : -INFINITY;
-                dead &= m[r] == -INFINITY;
-            }
-            dead = __syncthreads_and(dead);                                // also: the previous tile's fragment reads are done
-            if (tid == 0) tile_dead[jt] = dead;
-            live_tiles += !dead;
-            if (!dead) {
-#pragma unroll
-                for (int i = 0; i < NCH; ++i) {
-                    const int c = tid + 256 * i;
-                    *(h16x8 *) &tl[(c / CPR) * KP + (c % CPR) * 8] = pre[i];
-                }
-            }
-            __syncthreads();
-            if (j0 + AP_KT < c1) fetch_k(j0 + AP_KT);
-            f32x16v acc = {0};
-            if (!dead) {
-#pragma unroll
-                for (int kk = 0; kk < D / 16; ++kk) {
-                    const h16x8 kf = *(const h16x8 *) &tl[(32 * kw + l32) * KP + 16 * kk + 8 * hh];
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qf[kk], kf, acc, 0, 0, 0);
-                }
-            }
-            if (j < c1) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) S[(32 * tw + 8 * (r >> 2) + 4 * hh + (r & 3)) * SP + j - c0] = dead ? -INFINITY : acc[r] * g.scale + m[r];
-            }
-        }
-        __syncthreads();
-        if (live_tiles == 0) continue;                                     // block-uniform: the whole chunk is masked for these tokens
-        // 2. soft_max step: 16 rows per wave, <= 512 values = two float4 per lane; running max / sum per row
-        const int cw = c1 - c0;
-        typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-        for (int n4 = wave * 16; n4 < wave * 16 + 16; n4 += 4) {            // four rows at a time: their reads, reductions and exps interleave
-            float4 v[4][2];
-            float mx[4], m_old[4], m_new[4], sum[4], alpha[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float * row = S + (n4 + q) * SP;
-                mx[q] = -INFINITY;
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const int i = 4 * (lane + 64 * t);
-                    v[q][t] = i < cw ? *(const float4 *) (row + i) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-                    mx[q] = fmaxf(fmaxf(mx[q], fmaxf(v[q][t].x, v[q][t].y)), fmaxf(v[q][t].z, v[q][t].w));
-                }
-                m_old[q] = row_max[n4 + q];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) m_new[q] = fmaxf(m_old[q], wave_max(mx[q]));
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                sum[q] = 0.0f;
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    float4 & x = v[q][t];
-                    if (m_new[q] == -INFINITY) x = make_float4(0.f, 0.f, 0.f, 0.f);
-                    else { x.x = __expf(x.x - m_new[q]); x.y = __expf(x.y - m_new[q]); x.z = __expf(x.z - m_new[q]); x.w = __expf(x.w - m_new[q]); }
-                    sum[q] += x.x + x.y + x.z + x.w;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                sum[q] = wave_sum(sum[q]);
-                alpha[q] = m_old[q] == -INFINITY ? 0.0f : __expf(m_old[q] - m_new[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (single) {                                              // one chunk: normalise before the f16 rounding, exactly as the CPU path does
-                    const float inv = 1.0f / sum[q];
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) { v[q][t].x *= inv; v[q][t].y *= inv; v[q][t].z *= inv; v[q][t].w *= inv; }
-                    sum[q] = 1.0f;
-                }
-                const int nl = n4 + q;
-                if (lane == 0) { row_max[nl] = m_new[q]; row_sum[nl] = row_sum[nl] * alpha[q] + sum[q]; row_alpha[nl] = alpha[q]; }
-                _Float16 * prow = reinterpret_cast<_Float16 *>(S + nl * SP);    // p as f16 over the first half of the row's own bytes
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const int i = 4 * (lane + 64 * t);
-                    if (i < cw) *(h16x4 *) (prow + i) = h16x4{ (_Float16) v[q][t].x, (_Float16) v[q][t].y, (_Float16) v[q][t].z, (_Float16) v[q][t].w };
-                }
-            }
-        }
-        __syncthreads();                                                   // tile_dead, row_alpha and the p rows are visible to everyone
-        // 3. O = alpha * O + P V: wave (tw, kw) owns tokens 32 tw .. +32 and the d tiles kw * DT .. + DT; dead kv tiles are not loaded
-#pragma unroll
-        for (int t = 0; t < DT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[t][r] *= row_alpha[32 * tw + 8 * (r >> 2) + 4 * hh + (r & 3)];
-        auto fetch_v = [&](int j0) {
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                const int c = tid + 256 * i, row = c / VPR, col = c % VPR;
-                pre[i] = h16x8{0};
-                if (j0 + col * 8 < c1) pre[i] = *(const h16x8 *) (pv + (int64_t) row * g.v_nb1 + (int64_t) (j0 + col * 8) * 2);
-            }
-        };
-        int jn = c0, jtn = 0;                                              // next live tile
-        while (jn < c1 && tile_dead[jtn]) { jn += AP_KT; ++jtn; }
-        if (jn < c1) fetch_v(jn);
-        while (jn < c1) {
-            const int j0 = jn;
-            jn += AP_KT; ++jtn;
-            while (jn < c1 && tile_dead[jtn]) { jn += AP_KT; ++jtn; }
-            __syncthreads();                                               // the previous tile's fragment reads are done
-#pragma unroll
-            for (int i = 0; i < NCH; ++i) {
-                const int c = tid + 256 * i;
-                *(h16x8 *) &tl[(c / VPR) * VP + (c % VPR) * 8] = pre[i];
-            }
-            __syncthreads();
-            if (jn < c1) fetch_v(jn);
-#pragma unroll
-            for (int ks = 0; ks < AP_KT / 16; ++ks) {
-                if (j0 + 16 * ks >= c1) break;
-                const h16x8 pf = *(const h16x8 *) (reinterpret_cast<const _Float16 *>(S + (32 * tw + l32) * SP) + (j0 - c0) + 16 * ks + 8 * hh);
-#pragma unroll
-                for (int t = 0; t < DT; ++t) {
-                    const h16x8 vf = *(const h16x8 *) &tl[(32 * (kw * DT + t) + l32) * VP + 16 * ks + 8 * hh];
-                    oacc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pf, vf, oacc[t], 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();                                                   // the score tile and tile_dead are free for the next chunk
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < DT; ++t) {
-        const int d = 32 * (kw * DT + t) + l32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int nl = 32 * tw + 8 * (r >> 2) + 4 * hh + (r & 3), n = n0 + nl;
-            if (n < N) *(float *) (g.dst + (int64_t) n * g.d_nb1 + ((int64_t) h * g.Dv + d) * 4) = oacc[t][r] / row_sum[nl];
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ support predicates
 
 bool is_binary(int op) { return op >= QMM_OP_ADD && op <= QMM_OP_DIV; }
@@ -2155,78 +1309,6 @@ int qmm_op_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * a, const qmm_tensor * 
     return launch_rms_norm(ctx, ctx->s(stream), a, b, w, dst, sum, eps);
 }
 
-static bool attn_short_on() {                            // GGML_MI355X_ATTN_SHORT=0: the general kernel at every n_kv (A/B runs)
-    static const bool on = qmm_sw::read_one(qmm_sw::SW_ATTN_SHORT) != 0;
-    return on;
-}
-
-int qmm_attn_decode_supported(const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask, const qmm_tensor * dst) {
-    if (!q || !k || !v || !mask || !dst) return 0;
-    if (q->type != G_F32 || k->type != G_F16 || v->type != G_F16 || mask->type != G_F32 || dst->type != G_F32) return 0;
-    const int64_t D = k->ne[0], n_kv = k->ne[1], Hk = k->ne[2], N = q->ne[1], H = q->ne[2], Dv = v->ne[1];
-    if (D != 64 && D != 128 && D != 256) return 0;
-    if (q->ne[0] != D || v->ne[0] != n_kv || v->ne[2] != Hk || Hk <= 0 || H % Hk || q->ne[3] != 1 || k->ne[3] != 1 || v->ne[3] != 1) return 0;
-    if (N < 1 || N > 8 || n_kv < 8 || n_kv % 8 || n_kv > 16384 || Dv < 1 || Dv > 1024 || H > 65535) return 0;
-    if (q->nb[0] != 4 || k->nb[0] != 2 || v->nb[0] != 2 || mask->nb[0] != 4 || dst->nb[0] != 4) return 0;
-    if (mask->ne[0] != n_kv || mask->ne[1] < N || dst->ne[0] != Dv * H || dst->ne[1] != N || dst->ne[2] != 1 || dst->ne[3] != 1) return 0;
-    if (q->nb[1] % 4 || q->nb[2] % 4 || k->nb[1] % 16 || k->nb[2] % 16 || v->nb[1] % 16 || v->nb[2] % 16 || mask->nb[1] % 4 || dst->nb[1] % 4) return 0;
-    return 1;
-}
-
-int qmm_attn_decode(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask, const qmm_tensor * dst,
-                    float scale, void * stream) {
-    if (!ctx || !qmm_attn_decode_supported(q, k, v, mask, dst)) return fail(QMM_EUNSUPPORTED, "qmm_attn_decode: operands not supported");
-    if ((uintptr_t) k->data % 16 || (uintptr_t) v->data % 16) return fail(QMM_EINVAL, "qmm_attn_decode: K / V must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(ctx->device));
-    QMM_CHAIN_FLUSH(ctx);
-    AttnArgs g;
-    g.q = (const char *) q->data; g.k = (const char *) k->data; g.v = (const char *) v->data; g.mask = (const char *) mask->data; g.dst = (char *) dst->data;
-    g.q_nb1 = q->nb[1]; g.q_nb2 = q->nb[2]; g.k_nb1 = k->nb[1]; g.k_nb2 = k->nb[2]; g.v_nb1 = v->nb[1]; g.v_nb2 = v->nb[2];
-    g.m_nb1 = mask->nb[1]; g.d_nb1 = dst->nb[1];
-    g.D = (int32_t) k->ne[0]; g.Dv = (int32_t) v->ne[1]; g.n_kv = (int32_t) k->ne[1]; g.H = (int32_t) q->ne[2]; g.gqa = (int32_t) (q->ne[2] / k->ne[2]);
-    g.scale = scale;
-    const dim3 grid((unsigned) g.H, (unsigned) q->ne[1]);
-    const size_t lds = (size_t) g.n_kv * 4;
-    hipStream_t st = ctx->s(stream);
-    static const bool split_on = qmm_sw::read_one(qmm_sw::SW_ATTN_SPLIT) != 0;
-    if (split_on && g.n_kv >= 1024 && g.D <= 128) {
-        // kv range over S workgroups per (head, token), then the merge (long caches: one workgroup per head is latency-bound)
-        const int S = g.n_kv / 256 < 16 ? g.n_kv / 256 : 16;
-        const int chunk = ((g.n_kv + S - 1) / S + 7) / 8 * 8;
-        const int N = (int) q->ne[1];
-        const size_t bytes = (size_t) g.H * N * S * (g.Dv + 2) * sizeof(float);
-        int rc = ensure_ws(ctx, bytes);
-        if (rc) return rc;
-        float * part = (float *) ctx->ws;
-        const dim3 sgrid((unsigned) g.H, (unsigned) N, (unsigned) S);
-        if (g.D == 64) hipLaunchKernelGGL((attn_decode_split_kernel<64>), sgrid, dim3(1024), (size_t) chunk * 4, st, g, part, S, chunk);
-        else           hipLaunchKernelGGL((attn_decode_split_kernel<128>), sgrid, dim3(1024), (size_t) chunk * 4, st, g, part, S, chunk);
-        hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned) g.H, (unsigned) N), dim3(256), 0, st, (const float *) part, g.dst, g.d_nb1, g.Dv, S);
-        HIP_TRY(hipGetLastError());
-        return QMM_OK;
-    }
-    const AttnFresh none{};
-    if (attn_short_on() && g.n_kv <= 1024 && g.D <= 128 && g.Dv <= 128) {
-        const size_t lds2 = (size_t) g.n_kv * 8;
-        const int w = g.n_kv <= 256 ? 0 : g.n_kv <= 512 ? 1 : 2;
-        auto k64  = w == 0 ? attn_decode_short_kernel<64, false, 256> : w == 1 ? attn_decode_short_kernel<64, false, 512> : attn_decode_short_kernel<64, false, 1024>;
-        auto k128 = w == 0 ? attn_decode_short_kernel<128, false, 256> : w == 1 ? attn_decode_short_kernel<128, false, 512> : attn_decode_short_kernel<128, false, 1024>;
-        if (g.D == 64) hipLaunchKernelGGL(k64, grid, dim3(1024), lds2, st, g, none);
-        else           hipLaunchKernelGGL(k128, grid, dim3(1024), lds2, st, g, none);
-        HIP_TRY(hipGetLastError());
-        return QMM_OK;
-    }
-    if (g.D == 64) {
-        hipLaunchKernelGGL((attn_decode_kernel<64, false>), grid, dim3(1024), lds, st, g, none);
-    } else if (g.D == 128) {
-        hipLaunchKernelGGL((attn_decode_kernel<128, false>), grid, dim3(1024), lds, st, g, none);
-    } else {
-        hipLaunchKernelGGL((attn_decode_kernel<256, false>), grid, dim3(1024), lds, st, g, none);
-    }
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
-
 int qmm_rope_kv_store_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
                                 const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst) {
     if (!sup_rope(q, pos, ff, q_dst)) return 0;
@@ -2267,117 +1349,11 @@ int qmm_rope_kv_store(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * po
     return QMM_OK;
 }
 
-int qmm_attn_prefill_supported(const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask, const qmm_tensor * dst) {
-    if (!q || !k || !v || !mask || !dst) return 0;
-    if (q->type != G_F32 || k->type != G_F16 || v->type != G_F16 || mask->type != G_F32 || dst->type != G_F32) return 0;
-    const int64_t D = k->ne[0], n_kv = k->ne[1], Hk = k->ne[2], N = q->ne[1], H = q->ne[2], Dv = v->ne[1];
-    if ((D != 64 && D != 128) || Dv != D) return 0;
-    if (q->ne[0] != D || v->ne[0] != n_kv || v->ne[2] != Hk || Hk <= 0 || H % Hk || q->ne[3] != 1 || k->ne[3] != 1 || v->ne[3] != 1) return 0;
-    if (N < 1 || N > (1 << 20) || n_kv < 32 || n_kv % 32 || n_kv > (1 << 20) || H > 65535) return 0;
-    if (q->nb[0] != 4 || k->nb[0] != 2 || v->nb[0] != 2 || mask->nb[0] != 4 || dst->nb[0] != 4) return 0;
-    if (mask->ne[0] != n_kv || mask->ne[1] < N || dst->ne[0] != Dv * H || dst->ne[1] != N || dst->ne[2] != 1 || dst->ne[3] != 1) return 0;
-    if (q->nb[1] % 16 || q->nb[2] % 16 || k->nb[1] % 16 || k->nb[2] % 16 || v->nb[1] % 16 || v->nb[2] % 16 || mask->nb[1] % 4 || dst->nb[1] % 4) return 0;
-    return 1;
-}
+} // extern "C"
 
-int qmm_attn_prefill(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask, const qmm_tensor * dst,
-                     float scale, void * stream) {
-    if (!ctx || !qmm_attn_prefill_supported(q, k, v, mask, dst)) return fail(QMM_EUNSUPPORTED, "qmm_attn_prefill: operands not supported");
-    if ((uintptr_t) k->data % 16 || (uintptr_t) v->data % 16 || (uintptr_t) q->data % 16) return fail(QMM_EINVAL, "qmm_attn_prefill: q / K / V must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(ctx->device));
-    QMM_CHAIN_FLUSH(ctx);
-    AttnArgs g;
-    g.q = (const char *) q->data; g.k = (const char *) k->data; g.v = (const char *) v->data; g.mask = (const char *) mask->data; g.dst = (char *) dst->data;
-    g.q_nb1 = q->nb[1]; g.q_nb2 = q->nb[2]; g.k_nb1 = k->nb[1]; g.k_nb2 = k->nb[2]; g.v_nb1 = v->nb[1]; g.v_nb2 = v->nb[2];
-    g.m_nb1 = mask->nb[1]; g.d_nb1 = dst->nb[1];
-    g.D = (int32_t) k->ne[0]; g.Dv = (int32_t) v->ne[1]; g.n_kv = (int32_t) k->ne[1]; g.H = (int32_t) q->ne[2]; g.gqa = (int32_t) (q->ne[2] / k->ne[2]);
-    g.scale = scale;
-    const int N = (int) q->ne[1];
-    const dim3 grid((unsigned) ((N + AP_TN - 1) / AP_TN), (unsigned) g.H);
-    const size_t tile = (size_t) 128 * (AP_KT + 8) * 2;                      // >= K tile 64 x (D + 8) and V tile D x (64 + 8) halves, D <= 128
-    const size_t lds = (size_t) AP_TN * ((g.n_kv < AP_CH ? g.n_kv : AP_CH) + 4) * 4 + tile;
-    hipStream_t st = ctx->s(stream);
-    if (g.D == 128) {
-        auto kern = attn_prefill_kernel<128>;
-        if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, g, N);
-    } else {
-        auto kern = attn_prefill_kernel<64>;
-        if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, g, N);
-    }
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
+#include "qmm_attn.hiph"         // the attention kernels, their launch executor and entry points
 
-int qmm_attn_decode_rope_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_rope,
-                                   const qmm_tensor * k_new, const qmm_tensor * k_store, const qmm_tensor * v_new, const qmm_tensor * v_store,
-                                   const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask, const qmm_tensor * dst, int64_t j0) {
-    if (!q || !pos || !q_rope || !k_new || !k_store || !v_new || !v_store || !k || !v || !mask || !dst) return 0;
-    // q [D, H, N] un-roped (q_rope: the ROPE node, for its op_params); the permuted view of it is what qmm_attn_decode takes
-    qmm_tensor qp = *q;
-    qp.ne[1] = q->ne[2]; qp.ne[2] = q->ne[1]; qp.nb[1] = q->nb[2]; qp.nb[2] = q->nb[1];
-    if (!qmm_attn_decode_supported(&qp, k, v, mask, dst)) return 0;
-    if (!qmm_rope_kv_store_supported(q, pos, ff, q_rope, k_new, k_store, v_new, v_store)) return 0;
-    const int64_t D = k->ne[0], N = q->ne[2], Hk = k->ne[2], Dv = v->ne[1], n_kv = k->ne[1];
-    if (q_rope->op_params[2] != 0 || q_rope->op_params[1] != D || D > 128) return 0;                 // normal mode over the whole head
-    if (k_new->ne[0] != D || k_new->ne[1] != Hk || k_new->ne[2] != N || k_new->ne[3] != 1 || k_new->nb[0] != 4) return 0;
-    if (k_store->nb[0] != 2 || k_store->nb[1] % 2 || k_store->nb[2] % 2) return 0;
-    // v_new is v_cur^T [N, Dv * Hk] (element (n, c) at n * nb0 + c * nb1), v_store the transposed cache view [N, Dv * Hk]
-    if (v_new->ne[0] != N || v_new->ne[1] != Dv * Hk || v_new->ne[2] != 1 || v_new->ne[3] != 1 || v_new->nb[1] != 4) return 0;
-    if (v_store->ne[0] != N || v_store->ne[1] != Dv * Hk || v_store->nb[0] != 2 || v_store->nb[1] % 2) return 0;
-    if (j0 < 0 || j0 + N > n_kv) return 0;
-    return 1;
-}
-
-int qmm_attn_decode_rope(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_rope,
-                         const qmm_tensor * k_new, const qmm_tensor * k_store, const qmm_tensor * v_new, const qmm_tensor * v_store,
-                         const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask, const qmm_tensor * dst, float scale, int64_t j0,
-                         void * stream) {
-    if (!ctx || !qmm_attn_decode_rope_supported(q, pos, ff, q_rope, k_new, k_store, v_new, v_store, k, v, mask, dst, j0))
-        return fail(QMM_EUNSUPPORTED, "qmm_attn_decode_rope: operands not supported");
-    if ((uintptr_t) k->data % 16 || (uintptr_t) v->data % 16) return fail(QMM_EINVAL, "qmm_attn_decode_rope: K / V must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(ctx->device));
-    QMM_CHAIN_FLUSH(ctx);
-    AttnArgs g;
-    g.q = (const char *) q->data; g.k = (const char *) k->data; g.v = (const char *) v->data; g.mask = (const char *) mask->data; g.dst = (char *) dst->data;
-    g.q_nb1 = q->nb[2]; g.q_nb2 = q->nb[1];                                  // token stride, head stride of the un-permuted q
-    g.k_nb1 = k->nb[1]; g.k_nb2 = k->nb[2]; g.v_nb1 = v->nb[1]; g.v_nb2 = v->nb[2];
-    g.m_nb1 = mask->nb[1]; g.d_nb1 = dst->nb[1];
-    g.D = (int32_t) k->ne[0]; g.Dv = (int32_t) v->ne[1]; g.n_kv = (int32_t) k->ne[1]; g.H = (int32_t) q->ne[1]; g.gqa = (int32_t) (q->ne[1] / k->ne[2]);
-    g.scale = scale;
-    AttnFresh f;
-    f.kraw = (const char *) k_new->data; f.vraw = (const char *) v_new->data; f.kd = (char *) k_store->data; f.vd = (char *) v_store->data;
-    f.pos = (const int32_t *) pos->data; f.ff = ff ? (const float *) ff->data : nullptr;
-    f.kraw_nbh = k_new->nb[1]; f.kraw_nbn = k_new->nb[2]; f.vraw_nbn = v_new->nb[0];
-    f.kd_nbh = k_store->nb[1]; f.kd_nbn = k_store->nb[2]; f.vd_nbc = v_store->nb[1];
-    f.rp = rope_params(q_rope);
-    f.N = (int32_t) q->ne[2]; f.j0 = (int32_t) j0;
-    const dim3 grid((unsigned) g.H, (unsigned) f.N);
-    const size_t lds = (size_t) g.n_kv * 4 + (size_t) g.D * 4 + (size_t) f.N * (g.D + g.Dv) * 2;
-    hipStream_t st = ctx->s(stream);
-    if (attn_short_on() && g.n_kv <= 1024 && g.Dv <= 128) {            // (D <= 128: qmm_attn_decode_rope_supported)
-        const size_t lds2 = lds + (size_t) g.n_kv * 4;
-        const int w = g.n_kv <= 256 ? 0 : g.n_kv <= 512 ? 1 : 2;
-        auto k64  = w == 0 ? attn_decode_short_kernel<64, true, 256> : w == 1 ? attn_decode_short_kernel<64, true, 512> : attn_decode_short_kernel<64, true, 1024>;
-        auto k128 = w == 0 ? attn_decode_short_kernel<128, true, 256> : w == 1 ? attn_decode_short_kernel<128, true, 512> : attn_decode_short_kernel<128, true, 1024>;
-        if (g.D == 64) hipLaunchKernelGGL(k64, grid, dim3(1024), lds2, st, g, f);
-        else           hipLaunchKernelGGL(k128, grid, dim3(1024), lds2, st, g, f);
-        HIP_TRY(hipGetLastError());
-        return QMM_OK;
-    }
-    if (g.D == 64) {
-        auto kern = attn_decode_kernel<64, true>;
-        if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-        hipLaunchKernelGGL(kern, grid, dim3(1024), lds, st, g, f);
-    } else {
-        auto kern = attn_decode_kernel<128, true>;
-        if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-        hipLaunchKernelGGL(kern, grid, dim3(1024), lds, st, g, f);
-    }
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
+extern "C" {
 
 int qmm_moe_router_supported(const qmm_tensor * logits, const qmm_tensor * ids, const qmm_tensor * weights, int64_t n_used) {
     if (!logits || !ids || !weights || logits->type != G_F32 || ids->type != G_I32 || weights->type != G_F32) return 0;

@@ -219,7 +219,9 @@ QMM_API int qmm_chain_stats(const qmm_ctx * ctx, int * persistent_launches, int 
 QMM_API int qmm_chain_debug(qmm_ctx * ctx, void * stamps);
 
 /* Which kernels did a call issue?  Between qmm_trace_begin and qmm_trace_end every kernel launch of the MUL_MAT / MUL_MAT_ID entry
- * points appends its name (template arguments as rocprofv3 prints them, ';' behind each) to a host-side list; qmm_trace_end copies the
+ * points, of qmm_op_compute / qmm_op_add_rms_norm and of the attention entry points (qmm_attn_decode, qmm_attn_decode_rope,
+ * qmm_attn_prefill: e.g. "attn_decode_split_kernel<128>;attn_combine_kernel;") appends its name (template arguments as rocprofv3
+ * prints them, ';' behind each) to a host-side list; qmm_trace_end copies the
  * list into buf and returns the number of launches (< 0: error).  Host bookkeeping only, nothing on the device changes.  bench.py
  * buckets its roofline by these labels, so the figures describe the launches the timed pass issues (ggml has no counterpart: its CPU
  * backend has one code path per type, ggml-cpu.c:6745-6937). */

@@ -1,4 +1,4 @@
-// attn_dev.hip — development harness of the token-generation attention launch (csrc/qmm_ops.hip attn_decode_kernel<128, true>:
+// attn_dev.hip — development harness of the token-generation attention launch (csrc/qmm_attn.hiph attn_decode_kernel<128, true>:
 // rope(q), rope(k) -> K cache, v -> V cache, kq, softmax, kqv, merge heads in one launch): llama3-8b shape (32 heads, 8 kv heads,
 // D = 128), one new token into an n_kv = 256 window.  Prints the average duration behind a producer launch (so the new rows come
 // from another kernel's stores, as in the graph) and the 100 MHz phase stamps of the workgroups.
@@ -56,12 +56,13 @@ int main(int argc, char ** argv) {
     memset(&f.rp, 0, sizeof(f.rp));
     f.rp.n_dims = D; f.rp.theta_scale = powf(500000.0f, -2.0f / D); f.rp.freq_scale = 1.0f; f.rp.attn_factor = 1.0f;
     f.N = N; f.j0 = j0;
-    const size_t lds = (size_t) n_kv * 4 + (size_t) D * 4 + (size_t) N * (D + D) * 2;
-    int which = 1;                                      // 0: attn_decode_kernel (general), 1: attn_decode_short_kernel
+    // kernel, grid and LDS bytes as the library has them (qmm_attn_plan.h): with the short kernel switched off, and as by default
+    const AttnPlan plans[2] = { attn_decode_plan({ false, false }, D, D, n_kv, N, H, true), attn_decode_plan({ true, false }, D, D, n_kv, N, H, true) };
+    qmm_ctx ctx;
+    int which = 1;                                      // 0: attn_decode_kernel (general), 1: attn_decode_short_kernel (up to its 1024 columns)
     auto launch = [&](float seed) {
         hipLaunchKernelGGL(producer_kernel, dim3(16), dim3(256), 0, 0, q, kraw, vraw, H * D, Hk * D, seed);
-        if (which) hipLaunchKernelGGL((n_kv <= 256 ? attn_decode_short_kernel<128, true, 256> : n_kv <= 512 ? attn_decode_short_kernel<128, true, 512> : attn_decode_short_kernel<128, true, 1024>), dim3(H, N), dim3(1024), lds + (size_t) n_kv * 4, 0, g, f);
-        else       hipLaunchKernelGGL((attn_decode_kernel<128, true>), dim3(H, N), dim3(1024), lds, 0, g, f);
+        if (run_attn(&ctx, 0, plans[which], g, f)) { fprintf(stderr, "%s: not launched\n", plans[which].label); exit(2); }
     };
     // parity of the two kernels: output row and the stored cache rows
     std::vector<float> o0(H * D), o1(H * D);

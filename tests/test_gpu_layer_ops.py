@@ -232,31 +232,56 @@ def test_rope_kv_store_one_launch(qmm, n_tok, variant):
     assert not vc[:, :kv_head].any() and not vc[:, kv_head + n_tok:].any()
 
 
-@pytest.mark.parametrize("n_tok,n_kv,d", [(1, 640, 128), (3, 96, 128), (1, 32, 64), (8, 1024, 128), (2, 4160, 128), (1, 1056, 64), (3, 16384, 128),
-                                           (1, 96, 256), (3, 640, 256), (2, 1056, 256)])
-def test_attn_decode_one_launch(qmm, n_tok, n_kv, d):
-    """KQ -> soft_max(scale, mask) -> KQV -> merged heads, grouped-query, against f64 numpy with the CPU's f16 roundings of q and p"""
+def _short(d, fresh, width):
+    return (f"attn_decode_short_kernel<{d},{fresh},{width}>",)
+
+
+def _split(d):
+    return (f"attn_decode_split_kernel<{d}>", "attn_combine_kernel")
+
+
+# (n_tok, n_kv, d) or (n_tok, n_kv, d, dv), and the launches the case was written for: every width of the short kernel at both of its
+# ends, the first cache the split takes and one whose last piece is ragged (1032: 4 pieces of 264, the last 240 long), the general
+# kernel for D = 256 and for Dv > 128 (two passes of its d0 loop)
+ATTN_DECODE_CASES = [
+    ((1, 640, 128), _short(128, "false", 1024)), ((3, 96, 128), _short(128, "false", 256)), ((1, 32, 64), _short(64, "false", 256)),
+    ((8, 1024, 128), _split(128)), ((2, 4160, 128), _split(128)), ((1, 1056, 64), _split(64)), ((3, 16384, 128), _split(128)),
+    ((1, 96, 256), ("attn_decode_kernel<256,false>",)), ((3, 640, 256), ("attn_decode_kernel<256,false>",)),
+    ((2, 1056, 256), ("attn_decode_kernel<256,false>",)),
+    ((1, 256, 128), _short(128, "false", 256)), ((2, 264, 64), _short(64, "false", 512)), ((1, 512, 128), _short(128, "false", 512)),
+    ((3, 520, 128), _short(128, "false", 1024)), ((1, 1016, 64), _short(64, "false", 1024)), ((1, 1032, 128), _split(128)),
+    ((1, 512, 256), ("attn_decode_kernel<256,false>",)), ((2, 264, 64, 192), ("attn_decode_kernel<64,false>",)),
+]
+
+
+@pytest.mark.parametrize("shape,labels", ATTN_DECODE_CASES, ids=["-".join(map(str, c[0])) for c in ATTN_DECODE_CASES])
+def test_attn_decode_one_launch(qmm, shape, labels):
+    """KQ -> soft_max(scale, mask) -> KQV -> merged heads, grouped-query, against f64 numpy with the CPU's f16 roundings of q and p;
+    V rows of another width than K rows (dv) where the case has one"""
     from ggml_hexagon_amd import capi
+    n_tok, n_kv, d = shape[:3]
+    dv = shape[3] if len(shape) > 3 else d
     rng = np.random.default_rng(n_kv + n_tok)
     h, hk, n_ctx = 8, 2, n_kv + 64
     q = rng.normal(0, 1, (h, n_tok, d)).astype(np.float32)
     kc = rng.normal(0, 1, (n_ctx, hk, d)).astype(np.float16)
-    vc = rng.normal(0, 1, (hk, d, n_ctx)).astype(np.float16)
+    vc = rng.normal(0, 1, (hk, dv, n_ctx)).astype(np.float16)
     mask = np.zeros((64, n_kv), np.float32)
     for t in range(n_tok):
         mask[t, n_kv - (n_tok - 1 - t) * 3:] = -np.inf          # each token sees a different prefix
     mask[:, 5] = -np.inf
     scale = 1.0 / np.sqrt(d)
-    dq, dk, dv, dm = dev(q.transpose(1, 0, 2)), dev(kc), dev(vc), dev(mask)          # q_cur layout [n_tok, h, d], permuted view below
-    out = torch.empty((n_tok, h * d), device="cuda")
+    dq, dk, dvc, dm = dev(q.transpose(1, 0, 2)), dev(kc), dev(vc), dev(mask)         # q_cur layout [n_tok, h, d], permuted view below
+    out = torch.empty((n_tok, h * dv), device="cuda")
     tq = capi.QmmTensor.make(F32, [d, n_tok, h], nb=[4, h * d * 4, d * 4, n_tok * h * d * 4], data=dq.data_ptr())
     tk = capi.QmmTensor.make(F16, [d, n_kv, hk], nb=[2, hk * d * 2, d * 2, n_ctx * hk * d * 2], data=dk.data_ptr())
-    tv = capi.QmmTensor.make(F16, [n_kv, d, hk], nb=[2, n_ctx * 2, n_ctx * d * 2, n_ctx * d * hk * 2], data=dv.data_ptr())
+    tv = capi.QmmTensor.make(F16, [n_kv, dv, hk], nb=[2, n_ctx * 2, n_ctx * dv * 2, n_ctx * dv * hk * 2], data=dvc.data_ptr())
     tm = capi.QmmTensor.make(F32, [n_kv, 64], data=dm.data_ptr())
-    td = capi.QmmTensor.make(F32, [h * d, n_tok], data=out.data_ptr())
+    td = capi.QmmTensor.make(F32, [h * dv, n_tok], data=out.data_ptr())
     r = lambda t: capi.C.byref(t)
-    qmm._chk(qmm.lib.qmm_attn_decode(qmm.ctx, r(tq), r(tk), r(tv), r(tm), r(td), scale, qmm._stream()))
-    got = out.cpu().numpy().reshape(n_tok, h, d)
+    got_labels = qmm.trace(lambda: qmm._chk(qmm.lib.qmm_attn_decode(qmm.ctx, r(tq), r(tk), r(tv), r(tm), r(td), scale, qmm._stream())))
+    assert got_labels == labels, got_labels
+    got = out.cpu().numpy().reshape(n_tok, h, dv)
     qh = q.astype(np.float16).astype(np.float64)
     for hh in range(h):
         g = hh // (h // hk)
@@ -269,9 +294,11 @@ def test_attn_decode_one_launch(qmm, n_tok, n_kv, d):
         assert rel_rms(got[:, hh], want) < (5e-4 if n_kv < 1024 else 1.5e-3), (hh, n_tok, n_kv)
 
 
-@pytest.mark.parametrize("n_tok,n_kv,d", [(512, 512, 128), (70, 96, 128), (33, 64, 64), (200, 480, 128), (300, 1024, 128), (130, 2080, 128),
-                                           (64, 576, 64)])
-def test_attn_prefill_one_launch(qmm, n_tok, n_kv, d):
+@pytest.mark.parametrize("n_tok,n_kv,d,labels", [
+    (512, 512, 128, ("attn_prefill_kernel<128>",)), (70, 96, 128, ("attn_prefill_kernel<128>",)), (33, 64, 64, ("attn_prefill_kernel<64>",)),
+    (200, 480, 128, ("attn_prefill_kernel<128>",)), (300, 1024, 128, ("attn_prefill_kernel<128>",)), (130, 2080, 128, ("attn_prefill_kernel<128>",)),
+    (64, 576, 64, ("attn_prefill_kernel<64>",))], ids=["512-512-128", "70-96-128", "33-64-64", "200-480-128", "300-1024-128", "130-2080-128", "64-576-64"])
+def test_attn_prefill_one_launch(qmm, n_tok, n_kv, d, labels):
     """the same chain for a prompt batch with the scores held in LDS, 512 kv columns at a time (running max / sum beyond that):
     ragged token tiles, n_kv not a multiple of the 64-row K tile or of the chunk, D = 64 and 128, grouped-query, causal-style mask"""
     from ggml_hexagon_amd import capi
@@ -293,7 +320,8 @@ def test_attn_prefill_one_launch(qmm, n_tok, n_kv, d):
     tm = capi.QmmTensor.make(F32, [n_kv, n_pad], data=dm.data_ptr())
     td = capi.QmmTensor.make(F32, [h * d, n_tok], data=out.data_ptr())
     r = lambda t: capi.C.byref(t)
-    qmm._chk(qmm.lib.qmm_attn_prefill(qmm.ctx, r(tq), r(tk), r(tv), r(tm), r(td), scale, qmm._stream()))
+    got_labels = qmm.trace(lambda: qmm._chk(qmm.lib.qmm_attn_prefill(qmm.ctx, r(tq), r(tk), r(tv), r(tm), r(td), scale, qmm._stream())))
+    assert got_labels == labels, got_labels
     got = out.cpu().numpy().reshape(n_tok, h, d)
     qh = q.astype(np.float16).astype(np.float64)
     for hh in range(h):
@@ -308,14 +336,27 @@ def test_attn_prefill_one_launch(qmm, n_tok, n_kv, d):
         assert np.sqrt(np.mean((got[:, hh] - want) ** 2) / np.mean(want ** 2)) < (1e-4 if n_kv <= 512 else 4e-4)
 
 
-@pytest.mark.parametrize("n_tok,j0,d", [(1, 100, 128), (3, 45, 128), (8, 0, 64), (2, 254, 128)])
-def test_attn_decode_rope_one_launch(qmm, n_tok, j0, d):
+# (n_tok, j0, d), and the launch the case was written for (n_kv is j0 + n_tok rounded up to 32): each width of the short kernel with
+# fresh rows, the new rows at the last columns of a width (510), on both sides of the 1024 width's 512-column trip boundary (511) and
+# inside its second trip (700), more than 1024 preparation items (8 tokens at d = 128: 64 + 8 * 64 + 8 * 128 = 1600, two rounds of
+# the preparation loop), and past 1024 columns the general kernel
+ATTN_ROPE_CASES = [
+    ((1, 100, 128), _short(128, "true", 256)), ((3, 45, 128), _short(128, "true", 256)), ((8, 0, 64), _short(64, "true", 256)),
+    ((2, 254, 128), _short(128, "true", 256)),
+    ((1, 300, 128), _short(128, "true", 512)), ((2, 510, 64), _short(64, "true", 512)), ((2, 511, 128), _short(128, "true", 1024)),
+    ((3, 700, 128), _short(128, "true", 1024)), ((8, 296, 128), _short(128, "true", 512)), ((1, 1100, 128), ("attn_decode_kernel<128,true>",)),
+]
+
+
+@pytest.mark.parametrize("shape,labels", ATTN_ROPE_CASES, ids=["-".join(map(str, c[0])) for c in ATTN_ROPE_CASES])
+def test_attn_decode_rope_one_launch(qmm, shape, labels):
     """rope(q), rope(k) -> K cache, v -> V cache and the attention over the updated cache as ONE launch: the result and both
     caches against the two-step numpy reference (the new rows are used from LDS, never read back from the cache)"""
     from ggml_hexagon_amd import capi
+    n_tok, j0, d = shape
     rng = np.random.default_rng(900 + n_tok + j0)
-    h, hk, n_ctx = 8, 2, 320
     n_kv = (j0 + n_tok + 31) // 32 * 32
+    h, hk, n_ctx = 8, 2, n_kv + 64
     q = rng.normal(0, 1, (n_tok, h, d)).astype(np.float32)
     k = rng.normal(0, 1, (n_tok, hk, d)).astype(np.float32)
     v = rng.normal(0, 1, (n_tok, hk * d)).astype(np.float32)
@@ -347,8 +388,10 @@ def test_attn_decode_rope_one_launch(qmm, n_tok, j0, d):
     tm = M(F32, [n_kv, 64], data=dm.data_ptr())
     td = M(F32, [h * d, n_tok], data=out.data_ptr())
     r = lambda t: capi.C.byref(t)
-    qmm._chk(qmm.lib.qmm_attn_decode_rope(qmm.ctx, r(tq), r(M(I32, [n_tok], data=dpos.data_ptr())), None, r(tqr), r(tkn), r(tks), r(tvn), r(tvs),
-                                          r(tk), r(tv), r(tm), r(td), scale, j0, qmm._stream()))
+    tpos = M(I32, [n_tok], data=dpos.data_ptr())
+    got_labels = qmm.trace(lambda: qmm._chk(qmm.lib.qmm_attn_decode_rope(qmm.ctx, r(tq), r(tpos), None, r(tqr), r(tkn), r(tks), r(tvn), r(tvs),
+                                                                         r(tk), r(tv), r(tm), r(td), scale, j0, qmm._stream())))
+    assert got_labels == labels, got_labels
     want_k = rope_ref(k, pos, d, theta_scale).astype(np.float16)
     kc2, vc2 = dkc.cpu().numpy(), dvc.cpu().numpy()
     assert np.max(np.abs(kc2[j0:j0 + n_tok].astype(np.float32) - want_k.astype(np.float32))) < 4e-3

@@ -922,3 +922,196 @@ def test_matvec_rules_live_in_the_plan_header_only():
             assert not re.search(r"\b1(5|6)0\s*(\*\s*1024|<<\s*10)\b|\b1(536|638)00\b", code), where
             assert not re.search(r"\*\s*(\w+(\.|->))?k\s*\*\s*(5\s*/\s*4|11\s*/\s*8|21\s*/\s*8)", code, re.I), where
             assert not re.search(r"MOE_MATVEC_MAX_PAIRS *=", code), where
+
+
+# ---- the attention launch plan (csrc/qmm_attn_plan.h): kernel, instantiation, grid, block, LDS and the pieces of a cut cache
+
+ATTN_PLAN_HEADER = ROOT / "ggml-hexagon_amd" / "csrc" / "qmm_attn_plan.h"
+ATTN_SECTION = ROOT / "ggml-hexagon_amd" / "csrc" / "qmm_attn.hiph"
+ATTN_PLAN_PROBE = r"""
+#include "qmm_attn_plan.h"
+#include <cstdlib>
+#include <iostream>
+#include <sstream>
+#include <string>
+using namespace qmm;
+int main() {
+    std::string spec;
+    while (std::getline(std::cin, spec)) {          // D Dv n_kv N H fresh [SHORT=0] [SPLIT=0]  |  prefill D n_kv N H
+        std::istringstream in(spec);
+        std::string first, kv;
+        in >> first;
+        AttnPlan p;
+        if (first == "prefill") {
+            int D, n_kv, N, H;
+            in >> D >> n_kv >> N >> H;
+            p = attn_prefill_plan(D, n_kv, N, H);
+        } else {
+            AttnRules r = { true, true };
+            int Dv, n_kv, N, H, fresh;
+            in >> Dv >> n_kv >> N >> H >> fresh;
+            while (in >> kv) { if (kv == "SHORT=0") r.short_on = false; else if (kv == "SPLIT=0") r.split_on = false; else return 1; }
+            p = attn_decode_plan(r, atoi(first.c_str()), Dv, n_kv, N, H, fresh != 0);
+        }
+        printf("%s%s%s grid=%u,%u,%u block=%u lds=%zu attr=%d S=%d chunk=%d ws=%zu\n", p.label, p.label2[0] ? ";" : "", p.label2, p.grid[0], p.grid[1], p.grid[2],
+               p.block, p.lds, (int) p.lds_attr, p.S, p.chunk, p.ws_bytes);
+    }
+    return 0;
+}
+"""
+# (shape, what the launchers did with it before the plan existed).  A shape: D, Dv, n_kv, tokens, heads, fresh (1 = qmm_attn_decode_rope: the
+# batch's own K / V rows come with the launch) and the switches off their defaults; or "prefill" D, n_kv, tokens, heads.  The right-hand sides
+# were printed by the launch code of the commit before this header (qmm_attn_decode, qmm_attn_decode_rope, qmm_attn_prefill of qmm_ops.hip)
+# copied into a stand-alone program, never by the header; the labels name the instantiation that code's ladders picked.  attr: the launcher
+# raised the kernel's LDS limit first.  Every width of the short kernel at both of its ends, the first and the longest cache the split takes,
+# ragged pieces, D = 256, Dv > 128, fresh rows at each width and past them, one fresh launch past 64 KiB, each switch where it changes the answer.
+ATTN_PLAN_TABLE = [
+    ("64 64 8 1 8 0",
+     "attn_decode_short_kernel<64,false,256> grid=8,1,1 block=1024 lds=64 attr=0 S=0 chunk=0 ws=0"),
+    ("64 64 256 2 8 0",
+     "attn_decode_short_kernel<64,false,256> grid=8,2,1 block=1024 lds=2048 attr=0 S=0 chunk=0 ws=0"),
+    ("64 64 264 3 8 0",
+     "attn_decode_short_kernel<64,false,512> grid=8,3,1 block=1024 lds=2112 attr=0 S=0 chunk=0 ws=0"),
+    ("64 64 512 1 8 0",
+     "attn_decode_short_kernel<64,false,512> grid=8,1,1 block=1024 lds=4096 attr=0 S=0 chunk=0 ws=0"),
+    ("64 64 520 2 8 0",
+     "attn_decode_short_kernel<64,false,1024> grid=8,2,1 block=1024 lds=4160 attr=0 S=0 chunk=0 ws=0"),
+    ("64 64 1016 3 8 0",
+     "attn_decode_short_kernel<64,false,1024> grid=8,3,1 block=1024 lds=8128 attr=0 S=0 chunk=0 ws=0"),
+    ("64 64 1024 1 8 0",
+     "attn_decode_split_kernel<64>;attn_combine_kernel grid=8,1,4 block=1024 lds=1024 attr=0 S=4 chunk=256 ws=8448"),
+    ("64 64 1032 2 8 0",
+     "attn_decode_split_kernel<64>;attn_combine_kernel grid=8,2,4 block=1024 lds=1056 attr=0 S=4 chunk=264 ws=16896"),
+    ("64 64 4096 3 8 0",
+     "attn_decode_split_kernel<64>;attn_combine_kernel grid=8,3,16 block=1024 lds=1024 attr=0 S=16 chunk=256 ws=101376"),
+    ("64 64 4160 1 8 0",
+     "attn_decode_split_kernel<64>;attn_combine_kernel grid=8,1,16 block=1024 lds=1056 attr=0 S=16 chunk=264 ws=33792"),
+    ("64 64 16384 2 8 0",
+     "attn_decode_split_kernel<64>;attn_combine_kernel grid=8,2,16 block=1024 lds=4096 attr=0 S=16 chunk=1024 ws=67584"),
+    ("128 128 8 1 32 0",
+     "attn_decode_short_kernel<128,false,256> grid=32,1,1 block=1024 lds=64 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 256 2 32 0",
+     "attn_decode_short_kernel<128,false,256> grid=32,2,1 block=1024 lds=2048 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 264 3 32 0",
+     "attn_decode_short_kernel<128,false,512> grid=32,3,1 block=1024 lds=2112 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 512 1 32 0",
+     "attn_decode_short_kernel<128,false,512> grid=32,1,1 block=1024 lds=4096 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 520 2 32 0",
+     "attn_decode_short_kernel<128,false,1024> grid=32,2,1 block=1024 lds=4160 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 1016 3 32 0",
+     "attn_decode_short_kernel<128,false,1024> grid=32,3,1 block=1024 lds=8128 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 1024 1 32 0",
+     "attn_decode_split_kernel<128>;attn_combine_kernel grid=32,1,4 block=1024 lds=1024 attr=0 S=4 chunk=256 ws=66560"),
+    ("128 128 1032 2 32 0",
+     "attn_decode_split_kernel<128>;attn_combine_kernel grid=32,2,4 block=1024 lds=1056 attr=0 S=4 chunk=264 ws=133120"),
+    ("128 128 4096 3 32 0",
+     "attn_decode_split_kernel<128>;attn_combine_kernel grid=32,3,16 block=1024 lds=1024 attr=0 S=16 chunk=256 ws=798720"),
+    ("128 128 4160 1 32 0",
+     "attn_decode_split_kernel<128>;attn_combine_kernel grid=32,1,16 block=1024 lds=1056 attr=0 S=16 chunk=264 ws=266240"),
+    ("128 128 16384 2 32 0",
+     "attn_decode_split_kernel<128>;attn_combine_kernel grid=32,2,16 block=1024 lds=4096 attr=0 S=16 chunk=1024 ws=532480"),
+    ("256 256 512 1 8 0",
+     "attn_decode_kernel<256,false> grid=8,1,1 block=1024 lds=2048 attr=0 S=0 chunk=0 ws=0"),
+    ("256 256 520 3 8 0",
+     "attn_decode_kernel<256,false> grid=8,3,1 block=1024 lds=2080 attr=0 S=0 chunk=0 ws=0"),
+    ("256 256 4096 1 32 0",
+     "attn_decode_kernel<256,false> grid=32,1,1 block=1024 lds=16384 attr=0 S=0 chunk=0 ws=0"),
+    ("64 192 264 2 8 0",
+     "attn_decode_kernel<64,false> grid=8,2,1 block=1024 lds=1056 attr=0 S=0 chunk=0 ws=0"),
+    ("128 192 4160 2 8 0",
+     "attn_decode_split_kernel<128>;attn_combine_kernel grid=8,2,16 block=1024 lds=1056 attr=0 S=16 chunk=264 ws=198656"),
+    ("128 128 256 1 8 1",
+     "attn_decode_short_kernel<128,true,256> grid=8,1,1 block=1024 lds=3072 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 320 1 8 1",
+     "attn_decode_short_kernel<128,true,512> grid=8,1,1 block=1024 lds=3584 attr=0 S=0 chunk=0 ws=0"),
+    ("64 64 512 2 8 1",
+     "attn_decode_short_kernel<64,true,512> grid=8,2,1 block=1024 lds=4864 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 544 2 8 1",
+     "attn_decode_short_kernel<128,true,1024> grid=8,2,1 block=1024 lds=5888 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 704 3 8 1",
+     "attn_decode_short_kernel<128,true,1024> grid=8,3,1 block=1024 lds=7680 attr=0 S=0 chunk=0 ws=0"),
+    ("64 64 1024 1 32 1",
+     "attn_decode_short_kernel<64,true,1024> grid=32,1,1 block=1024 lds=8704 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 1120 1 8 1",
+     "attn_decode_kernel<128,true> grid=8,1,1 block=1024 lds=5504 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 320 8 8 1",
+     "attn_decode_short_kernel<128,true,512> grid=8,8,1 block=1024 lds=7168 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 16384 1 32 1",
+     "attn_decode_kernel<128,true> grid=32,1,1 block=1024 lds=66560 attr=1 S=0 chunk=0 ws=0"),
+    ("64 192 256 2 8 1",
+     "attn_decode_kernel<64,true> grid=8,2,1 block=1024 lds=2304 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 1024 1 8 0 SPLIT=0",
+     "attn_decode_short_kernel<128,false,1024> grid=8,1,1 block=1024 lds=8192 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 4096 1 8 0 SPLIT=0",
+     "attn_decode_kernel<128,false> grid=8,1,1 block=1024 lds=16384 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 256 1 8 0 SHORT=0",
+     "attn_decode_kernel<128,false> grid=8,1,1 block=1024 lds=1024 attr=0 S=0 chunk=0 ws=0"),
+    ("128 128 256 1 8 1 SHORT=0",
+     "attn_decode_kernel<128,true> grid=8,1,1 block=1024 lds=2048 attr=0 S=0 chunk=0 ws=0"),
+    ("64 64 1024 2 8 0 SHORT=0 SPLIT=0",
+     "attn_decode_kernel<64,false> grid=8,2,1 block=1024 lds=4096 attr=0 S=0 chunk=0 ws=0"),
+    ("prefill 64 32 33 8",
+     "attn_prefill_kernel<64> grid=1,8,1 block=256 lds=27648 attr=0 S=0 chunk=0 ws=0"),
+    ("prefill 128 480 200 8",
+     "attn_prefill_kernel<128> grid=4,8,1 block=256 lds=142336 attr=1 S=0 chunk=0 ws=0"),
+    ("prefill 128 512 512 32",
+     "attn_prefill_kernel<128> grid=8,32,1 block=256 lds=150528 attr=1 S=0 chunk=0 ws=0"),
+    ("prefill 128 2080 130 8",
+     "attn_prefill_kernel<128> grid=3,8,1 block=256 lds=150528 attr=1 S=0 chunk=0 ws=0"),
+    ("prefill 64 512 33 8",
+     "attn_prefill_kernel<64> grid=1,8,1 block=256 lds=150528 attr=1 S=0 chunk=0 ws=0"),
+    ("prefill 64 2080 512 32",
+     "attn_prefill_kernel<64> grid=8,32,1 block=256 lds=150528 attr=1 S=0 chunk=0 ws=0"),
+    ("prefill 128 96 70 8",
+     "attn_prefill_kernel<128> grid=2,8,1 block=256 lds=44032 attr=0 S=0 chunk=0 ws=0"),
+]
+
+
+@pytest.fixture(scope="module")
+def attn_plan_probe(tmp_path_factory):
+    """the plan header alone, compiled by the host compiler (no HIP, no ggml) into a program that prints the plan of each shape on its input"""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    d = tmp_path_factory.mktemp("attnplan")
+    (d / "probe.cpp").write_text(ATTN_PLAN_PROBE)
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", f"-I{ATTN_PLAN_HEADER.parent}", str(d / "probe.cpp"), "-o", str(d / "probe")], check=True)
+    return lambda specs: subprocess.run([str(d / "probe")], input="\n".join(specs) + "\n", check=True, capture_output=True, text=True).stdout.splitlines()
+
+
+def test_attn_plan_keeps_every_decision(attn_plan_probe):
+    assert len(ATTN_PLAN_TABLE) >= 30
+    got = attn_plan_probe([spec for spec, _ in ATTN_PLAN_TABLE])
+    assert len(got) == len(ATTN_PLAN_TABLE)
+    for (spec, want), line in zip(ATTN_PLAN_TABLE, got):
+        assert line == want, spec
+
+
+def test_attn_rules_live_in_one_place():
+    """the plan functions and the shape predicate are defined in the plan header only; the two switches are read in one function of the
+    attention section; no other file launches an attention kernel; the development harness asks the plan (comments may speak of all this)"""
+    def code_of(f):
+        return [re.sub(r"//.*$", "", line) for line in f.read_text().splitlines()]
+    defines = re.compile(r"\b(AttnPlan|bool)\s+(attn_decode_plan|attn_prefill_plan|attn_shape_ok)\s*\(")
+    assert sorted(m.group(2) for line in code_of(ATTN_PLAN_HEADER) for m in defines.finditer(line)) == ["attn_decode_plan", "attn_prefill_plan", "attn_shape_ok"]
+    for f in sorted((ROOT / "ggml-hexagon_amd" / "csrc").iterdir()):
+        if f.suffix not in (".cpp", ".h", ".hip", ".hiph"):
+            continue
+        code = code_of(f)
+        inside = None                                                        # the function a line belongs to: the last line that opened one at column 0
+        for n, line in enumerate(code, 1):
+            where = f"{f.name}:{n}: {line.strip()[:120]}"
+            if re.match(r"^\w.*\)\s*\{", line):
+                inside = line
+            if f != ATTN_PLAN_HEADER:
+                assert not defines.search(line), where
+            if f != SWITCH_HEADER and re.search(r"\bSW_ATTN_(SHORT|SPLIT)\b", line):
+                assert f == ATTN_SECTION and inside is not None and re.search(r"\battn_rules\s*\(\)", inside), where
+            if f != ATTN_SECTION:
+                assert not re.search(r"hipLaunchKernelGGL\s*\(\s*\(*\s*attn_", line), where
+    dev = (ROOT / "profiles" / "tools" / "attn_dev.hip")
+    for n, line in enumerate(code_of(dev), 1):
+        assert not re.search(r"n_kv\s*<=", line), f"{dev.name}:{n}: {line.strip()[:120]}"
+    assert any("attn_decode_plan" in line for line in code_of(dev))
