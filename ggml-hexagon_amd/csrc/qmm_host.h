@@ -72,14 +72,10 @@ struct qmm_ctx {
     int         chain_checked = 0;   // chain_launches when the error word was last read
     hipStream_t chain_stream = nullptr;         // stream of the recorded steps
     char        name[128] = {0};
-    // qmm_trace_begin / qmm_trace_end: while set, every kernel launch of the MUL_MAT path, of the glue launchers behind qmm_op_compute /
-    // qmm_op_add_rms_norm (qmm_ops.hip) and of the attention entry points (qmm_attn.hiph) appends its label here (host side only; bench.py buckets its roofline by the kernels a call actually
+    // qmm_trace_begin / qmm_trace_end: while set, every kernel launch of the MUL_MAT path, of the glue launches behind qmm_op_compute /
+    // qmm_op_add_rms_norm (run_glue of qmm_ops.hip) and of the attention entry points (qmm_attn.hiph) appends its label here (host side only; bench.py buckets its roofline by the kernels a call actually
     // issued, not by a replica of the dispatch rules; tests/test_gpu_glue_ops.py asserts the branch each of its cases was written for).
-    // The glue labels, one per launch, name the kernel and the branch taken:
-    //   binary_kernel<vec> binary_kernel<scalar>   unary_kernel   rms_norm_vec_kernel<1024> rms_norm_vec_kernel<256> rms_norm_kernel   norm_kernel
-    //   soft_max_wave_kernel<1> <2> <4> (float4 per lane)   soft_max_kernel<lds> soft_max_kernel<dst> (where the row is staged)   rope_kernel
-    //   memcpy (also when src == dst and nothing is copied)   cpy_kernel   cpy_transpose_kernel   get_rows_kernel   get_rows_q_kernel<type id>
-    //   mul_mat_f16_kernel<vec> mul_mat_f16_kernel<scalar>   mul_mat_dot_block_kernel   mul_mat_dot_kernel   argsort_kernel   sum_rows_kernel
+    // The glue labels, one per launch, name the kernel and the branch taken: the table GLUE_LABELS of qmm_glue_plan.h.
     // The attention labels are the plan's (qmm_attn_plan.h), spelled as rocprofv3 prints the kernels:
     //   attn_decode_short_kernel<D,fresh,width>   attn_decode_kernel<D,fresh>   attn_decode_split_kernel<D> then attn_combine_kernel   attn_prefill_kernel<D>
     // Untraced, a launch pays one pointer test.

@@ -2,12 +2,15 @@
 // gfx950 only, no CPU path.  Every kernel is HBM-bound elementwise / row work except the small F16 attention matmuls,
 // which run on v_mfma_f32_32x32x16_f16.  Semantics follow the ggml CPU backend; each kernel cites the function it restates.
 // Parity: the reference's tests/test-backend-ops.cpp (built unmodified into oracle/_ref) against the CPU backend.
+// The file holds the kernels, run_glue and the C entry points.  Which operands an entry point takes, and for operands it takes which
+// kernel runs with which template arguments, grid, block, LDS bytes and trace label, is decided by qmm_glue_plan.h; run_glue launches
+// a plan and decides nothing; an entry point is its context check, the support predicate, the chain flush, the plan and the run.
 // The attention launches (AttnArgs, AttnFresh, the five attn_* kernels, qmm_attn_decode / _decode_rope / _prefill and their
-// _supported predicates) are a section of their own, qmm_attn.hiph, included below behind qmm_rope_kv_store; what they launch
-// for a shape is decided by qmm_attn_plan.h.  The rope and MoE glue entry points stay here.
+// _supported predicates) are a section of their own, qmm_attn.hiph, included below in front of the entry points; what they launch
+// for a shape is decided by qmm_attn_plan.h.
 
 #include "qmm_host.h"
-#include "../../include/ggml_mi355x_ops.h"
+#include "qmm_glue_plan.h"
 #include "qmm_device.hiph"
 
 #include <hip/hip_fp16.h>
@@ -17,10 +20,7 @@ using namespace qmm;
 
 namespace {
 
-enum : int { G_F32 = 0, G_F16 = 1, G_I32 = 26 };
-
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-constexpr int DOT_T = 128;           // threads per dst element of mul_mat_dot_block_kernel / per expert of moe_router_logits_kernel
 typedef float    f32x16v __attribute__((ext_vector_type(16)));
 
 struct Shape {           // extents and byte strides of one operand
@@ -31,28 +31,6 @@ Shape shape_of(const qmm_tensor * t) {
     Shape s;
     for (int i = 0; i < 4; ++i) { s.ne[i] = t->ne[i]; s.nb[i] = t->nb[i]; }
     return s;
-}
-int64_t nelements(const qmm_tensor * t) { return t->ne[0] * t->ne[1] * t->ne[2] * t->ne[3]; }
-int64_t nrows(const qmm_tensor * t) { return t->ne[1] * t->ne[2] * t->ne[3]; }
-int     esize(int type) { return type == G_F32 || type == G_I32 ? 4 : type == G_F16 ? 2 : 0; }
-bool    same_shape(const qmm_tensor * a, const qmm_tensor * b) {
-    return a->ne[0] == b->ne[0] && a->ne[1] == b->ne[1] && a->ne[2] == b->ne[2] && a->ne[3] == b->ne[3];
-}
-bool contiguous(const qmm_tensor * t) {
-    const int es = esize(t->type);
-    if (!es) return false;
-    int64_t nb = es;
-    for (int i = 0; i < 4; ++i) {
-        if (t->ne[i] != 1 && t->nb[i] != nb) return false;
-        nb *= t->ne[i];
-    }
-    return true;
-}
-// rows are dense runs of elements (nb[0] == element size); rows themselves may sit anywhere
-bool dense_rows(const qmm_tensor * t) { return esize(t->type) && (t->nb[0] == esize(t->type) || t->ne[0] == 1); }
-bool fits_u32(const qmm_tensor * t) { return nelements(t) < ((int64_t) 1 << 31); }
-bool aligned_to(const qmm_tensor * t, int a) {
-    return (uintptr_t) t->data % a == 0 && t->nb[1] % a == 0 && t->nb[2] % a == 0 && t->nb[3] % a == 0;
 }
 
 // wave_sum / wave_max: the DPP reductions of qmm_device.hiph (no LDS-permute traffic; the __shfl_xor butterflies this file began
@@ -500,7 +478,6 @@ cpy_transpose_kernel(const char * __restrict__ x, char * __restrict__ y, const u
 // The grid is the concatenation of the three index spaces; k and v parts are optional (nk = 0 / nv = 0).
 // the same for ROPE_HC heads of one (pair, token): cos / sin (the double-precision reduction and two polynomials, ~150 instructions) once for
 // all of them; round 3: one thread per (pair, head, token) made the 512-token launch ALU-bound at 14.5 us for 22 MB of traffic
-constexpr uint32_t ROPE_HC = 8;
 template <typename TD>
 __device__ __forceinline__ void rope_pair_heads(const char * __restrict__ x, const int32_t * __restrict__ pos, const float * __restrict__ ff,
                                                 char * __restrict__ y, const Shape & sx, const Shape & sy, const RopeParams & rp, const uint32_t gid) {
@@ -521,10 +498,6 @@ __device__ __forceinline__ void rope_pair_heads(const char * __restrict__ x, con
         else      { py[ia] = (TD) (x0 * c - x1 * s); py[ib] = (TD) (x0 * s + x1 * c); }
     }
 }
-__host__ __device__ inline uint32_t rope_heads_threads(const Shape & sx) {       // threads rope_pair_heads wants for a tensor
-    return (uint32_t) (sx.ne[0] / 2 * ((sx.ne[1] + ROPE_HC - 1) / ROPE_HC) * sx.ne[2] * sx.ne[3]);
-}
-
 struct RopeStoreArgs {
     const char * q; char * qd; const char * k; char * kd; const char * v; char * vd;
     const int32_t * pos; const float * ff;
@@ -652,7 +625,7 @@ struct MmArgs {
     int64_t a_nb1, a_nb2, a_nb3, b_nb1, b_nb2, b_nb3, d_nb1, d_nb2, d_nb3;
     int32_t M, N, K, ne12, r2, r3;
 };
-constexpr int MM_T = 64, MM_BK = 32, MM_LD = MM_BK + 8;      // LDS row pitch 80 B: 16-byte reads of 32 rows spread over all banks
+constexpr int MM_BK = 32, MM_LD = MM_BK + 8;      // LDS row pitch 80 B: 16-byte reads of 32 rows spread over all banks
 
 template <bool VEC>
 __global__ void __launch_bounds__(256)
@@ -938,201 +911,7 @@ mul_mat_dot_kernel(const MmArgs g) {
     if (lane == 0) *(float *) (g.d + (int64_t) i12 * g.d_nb2 + (int64_t) i13 * g.d_nb3 + (int64_t) n * g.d_nb1 + (int64_t) m * 4) = s;
 }
 
-// ------------------------------------------------------------------------------------------------ support predicates
-
-bool is_binary(int op) { return op >= QMM_OP_ADD && op <= QMM_OP_DIV; }
-bool is_unary(int op) { return op >= QMM_OP_SCALE && op <= QMM_OP_EXP; }
-bool quant_type(int t) { return type_known(t); }
-int  quant_blck(int t) { return type_blck(t); }
-
-bool sup_binary(const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d) {
-    if (!a || !b || !d || a->type != G_F32 || b->type != G_F32 || d->type != G_F32) return false;
-    if (!same_shape(a, d) || !dense_rows(a) || !dense_rows(d) || !fits_u32(d) || nelements(d) == 0) return false;
-    for (int i = 0; i < 4; ++i) if (b->ne[i] <= 0 || d->ne[i] % b->ne[i]) return false;       // ggml_can_repeat(b, a)
-    return a->nb[1] % 4 == 0 && a->nb[2] % 4 == 0 && a->nb[3] % 4 == 0 && b->nb[0] % 4 == 0 && b->nb[1] % 4 == 0 && b->nb[2] % 4 == 0 &&
-           b->nb[3] % 4 == 0;
-}
-bool sup_unary(const qmm_tensor * a, const qmm_tensor * d) {
-    return a && d && a->type == G_F32 && d->type == G_F32 && same_shape(a, d) && contiguous(a) && contiguous(d) && fits_u32(d);
-}
-bool sup_rms_norm(const qmm_tensor * a, const qmm_tensor * d) {
-    return a && d && a->type == G_F32 && d->type == G_F32 && same_shape(a, d) && dense_rows(a) && dense_rows(d) && fits_u32(d) &&
-           nelements(d) > 0;
-}
-bool sup_rope(const qmm_tensor * a, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * d) {
-    if (!a || !pos || !d || a->type != G_F32 || d->type != G_F32 || pos->type != G_I32 || !same_shape(a, d)) return false;
-    if (!dense_rows(a) || !dense_rows(d) || !contiguous(pos) || !fits_u32(d) || nelements(d) == 0 || a->ne[0] % 2) return false;
-    const int n_dims = d->op_params[1], mode = d->op_params[2];
-    if (mode != 0 && mode != 2) return false;                                     // normal or NEOX; no M-RoPE / vision
-    if (n_dims <= 0 || n_dims % 2 || n_dims > a->ne[0] || pos->ne[0] != a->ne[2]) return false;
-    if (ff && (ff->type != G_F32 || ff->ne[0] < n_dims / 2 || !contiguous(ff))) return false;
-    return true;
-}
-bool sup_soft_max(const qmm_tensor * a, const qmm_tensor * mask, const qmm_tensor * d) {
-    if (!a || !d || a->type != G_F32 || d->type != G_F32 || !same_shape(a, d) || !contiguous(a) || !contiguous(d)) return false;
-    if (nelements(d) == 0 || nrows(d) >= ((int64_t) 1 << 31)) return false;
-    if (mask) {
-        if (mask->type != G_F32 && mask->type != G_F16) return false;
-        if (!contiguous(mask) || mask->ne[0] != a->ne[0] || mask->ne[1] < a->ne[1] || mask->ne[2] != 1 || mask->ne[3] != 1) return false;
-    }
-    return true;
-}
-bool sup_cpy(const qmm_tensor * a, const qmm_tensor * d) {
-    if (!a || !d || !esize(a->type) || !esize(d->type) || a->type == G_I32 || d->type == G_I32) return false;
-    return nelements(a) == nelements(d) && fits_u32(a) && a->nb[0] % esize(a->type) == 0 && d->nb[0] % esize(d->type) == 0;
-}
-bool sup_get_rows(const qmm_tensor * a, const qmm_tensor * ids, const qmm_tensor * d) {
-    if (!a || !ids || !d || ids->type != G_I32 || d->type != G_F32 || !dense_rows(d) || nelements(d) == 0) return false;
-    if (d->ne[0] != a->ne[0] || d->ne[1] != ids->ne[0] || d->ne[2] != ids->ne[1] || d->ne[3] != ids->ne[2] || ids->ne[3] != 1) return false;
-    if (a->ne[2] != ids->ne[1] || a->ne[3] != ids->ne[2] || nrows(d) >= ((int64_t) 1 << 31)) return false;
-    if (quant_type(a->type)) return a->ne[0] % quant_blck(a->type) == 0 && a->nb[1] % 2 == 0;
-    return (a->type == G_F32 || a->type == G_F16) && dense_rows(a);
-}
-bool sup_mul_mat_f(const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d) {
-    if (!a || !b || !d || (a->type != G_F16 && a->type != G_F32) || b->type != G_F32 || d->type != G_F32) return false;
-    if (a->ne[0] != b->ne[0] || d->ne[0] != a->ne[1] || d->ne[1] != b->ne[1] || d->ne[2] != b->ne[2] || d->ne[3] != b->ne[3]) return false;
-    if (a->ne[2] <= 0 || a->ne[3] <= 0 || b->ne[2] % a->ne[2] || b->ne[3] % a->ne[3] || nelements(d) == 0 || a->ne[0] == 0) return false;
-    if (a->nb[0] != esize(a->type) || b->nb[0] != 4 || d->nb[0] != 4) return false;         // K dense in both operands
-    if (b->ne[2] * b->ne[3] > 65535 || a->ne[1] >= ((int64_t) 1 << 30) || b->ne[1] >= ((int64_t) 1 << 22)) return false;
-    return a->nb[1] % esize(a->type) == 0 && a->nb[2] % esize(a->type) == 0 && a->nb[3] % esize(a->type) == 0 && b->nb[1] % 4 == 0 &&
-           b->nb[2] % 4 == 0 && b->nb[3] % 4 == 0 && d->nb[1] % 4 == 0 && d->nb[2] % 4 == 0 && d->nb[3] % 4 == 0;
-}
-
-// ------------------------------------------------------------------------------------------------ launchers
-
-template <int OP>
-int launch_binary(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d) {
-    const uint32_t rows = (uint32_t) nrows(d);
-    const bool vec = d->ne[0] % 4 == 0 && b->ne[0] == d->ne[0] && b->nb[0] == 4 && aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(d, 16);
-    const uint32_t per_row = (uint32_t) (vec ? d->ne[0] / 4 : d->ne[0]);
-    const uint32_t rpb = per_row >= 256 ? 1 : 256 / per_row;
-    const dim3 grid((rows + rpb - 1) / rpb);
-    if (vec) QMM_TRACE(ctx, "binary_kernel<vec>");
-    else     QMM_TRACE(ctx, "binary_kernel<scalar>");
-    if (vec) hipLaunchKernelGGL((binary_kernel<OP, true>), grid, dim3(256), 0, st, (const char *) a->data, (const char *) b->data, (char *) d->data,
-                                shape_of(a), shape_of(b), shape_of(d), rows);
-    else     hipLaunchKernelGGL((binary_kernel<OP, false>), grid, dim3(256), 0, st, (const char *) a->data, (const char *) b->data, (char *) d->data,
-                                shape_of(a), shape_of(b), shape_of(d), rows);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
-
-template <int OP, bool MUL2>
-int launch_unary(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d, float p) {
-    const uint32_t n = (uint32_t) nelements(d);
-    if (n == 0) return QMM_OK;
-    QMM_TRACE(ctx, "unary_kernel");
-    hipLaunchKernelGGL((unary_kernel<OP, MUL2>), dim3((n + 1023) / 1024), dim3(256), 0, st, (const float *) a->data,
-                       b ? (const float *) b->data : nullptr, (float *) d->data, n, p);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
-
-template <typename TS, typename TD>
-int launch_cpy_t(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * d) {
-    const uint32_t n = (uint32_t) nelements(a);
-    // transposed source into dense rows (the V-cache store): 2-D, same extents, src dense along dim 1, dst dense along dim 0
-    if (a->ne[2] == 1 && a->ne[3] == 1 && d->ne[2] == 1 && d->ne[3] == 1 && a->ne[0] == d->ne[0] && a->ne[1] == d->ne[1] &&
-        a->nb[1] == (int64_t) sizeof(TS) && d->nb[0] == (int64_t) sizeof(TD) && a->ne[0] >= 32 && a->ne[1] >= 8) {
-        QMM_TRACE(ctx, "cpy_transpose_kernel");
-        hipLaunchKernelGGL((cpy_transpose_kernel<TS, TD>), dim3((unsigned) ((a->ne[0] + 31) / 32), (unsigned) ((a->ne[1] + 31) / 32)), dim3(256), 0, st,
-                           (const char *) a->data, (char *) d->data, (uint32_t) a->ne[0], (uint32_t) a->ne[1], a->nb[0], d->nb[1]);
-    } else {
-        QMM_TRACE(ctx, "cpy_kernel");
-        hipLaunchKernelGGL((cpy_kernel<TS, TD>), dim3((n + 255) / 256), dim3(256), 0, st, (const char *) a->data, (char *) d->data, shape_of(a),
-                           shape_of(d), n);
-    }
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
-int launch_cpy(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * d) {
-    if (nelements(a) == 0) return QMM_OK;
-    if (a->type == d->type && contiguous(a) && contiguous(d)) {
-        QMM_TRACE(ctx, "memcpy");
-        if (a->data != d->data) HIP_TRY(hipMemcpyAsync(d->data, a->data, (size_t) nelements(a) * esize(a->type), hipMemcpyDeviceToDevice, st));
-        return QMM_OK;
-    }
-    if (a->type == G_F32 && d->type == G_F32) return launch_cpy_t<float, float>(ctx, st, a, d);
-    if (a->type == G_F32 && d->type == G_F16) return launch_cpy_t<float, __half>(ctx, st, a, d);
-    if (a->type == G_F16 && d->type == G_F16) return launch_cpy_t<__half, __half>(ctx, st, a, d);
-    return launch_cpy_t<__half, float>(ctx, st, a, d);
-}
-
-template <int T>
-int launch_get_rows_q(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * ids, const qmm_tensor * d) {
-    QMM_TRACE(ctx, "get_rows_q_kernel<%d>", T);
-    hipLaunchKernelGGL((get_rows_q_kernel<T>), dim3((unsigned) nrows(d)), dim3(256), 0, st, (const uint8_t *) a->data, (const char *) ids->data,
-                       (char *) d->data, shape_of(a), shape_of(ids), shape_of(d));
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
-
-int launch_mul_mat_f(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d) {
-    MmArgs g;
-    g.a = (const char *) a->data;  g.b = (const char *) b->data;  g.d = (char *) d->data;
-    g.a_nb1 = a->nb[1]; g.a_nb2 = a->nb[2]; g.a_nb3 = a->nb[3];
-    g.b_nb1 = b->nb[1]; g.b_nb2 = b->nb[2]; g.b_nb3 = b->nb[3];
-    g.d_nb1 = d->nb[1]; g.d_nb2 = d->nb[2]; g.d_nb3 = d->nb[3];
-    g.M = (int32_t) a->ne[1]; g.N = (int32_t) b->ne[1]; g.K = (int32_t) a->ne[0];
-    g.ne12 = (int32_t) b->ne[2]; g.r2 = (int32_t) (b->ne[2] / a->ne[2]); g.r3 = (int32_t) (b->ne[3] / a->ne[3]);
-    const unsigned batch = (unsigned) (b->ne[2] * b->ne[3]);
-    if (a->type == G_F16) {
-        const dim3 grid((g.M + MM_T - 1) / MM_T, (g.N + MM_T - 1) / MM_T, batch);
-        const bool vec = aligned_to(a, 16) && aligned_to(b, 16);
-        if (vec) { QMM_TRACE(ctx, "mul_mat_f16_kernel<vec>");    hipLaunchKernelGGL((mul_mat_f16_kernel<true>), grid, dim3(256), 0, st, g); }
-        else     { QMM_TRACE(ctx, "mul_mat_f16_kernel<scalar>"); hipLaunchKernelGGL((mul_mat_f16_kernel<false>), grid, dim3(256), 0, st, g); }
-    } else {
-        const int64_t e = (int64_t) g.M * g.N;
-        if (e <= 2048 && g.K >= 1024) { QMM_TRACE(ctx, "mul_mat_dot_block_kernel"); hipLaunchKernelGGL(mul_mat_dot_block_kernel, dim3((unsigned) e, 1, batch), dim3(DOT_T), 0, st, g); }
-        else                          { QMM_TRACE(ctx, "mul_mat_dot_kernel");       hipLaunchKernelGGL((mul_mat_dot_kernel<float>), dim3((unsigned) ((e + 3) / 4), 1, batch), dim3(256), 0, st, g); }
-    }
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
-
-template <bool MUL, bool ADD>
-int launch_rms_norm_vec(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * d, const qmm_tensor * sum,
-                        float eps) {
-    const unsigned rows = (unsigned) nrows(d);
-    const bool wide = rows < 256 || a->ne[0] > 256 * 16;
-    const Shape sb = b ? shape_of(b) : shape_of(a), ss = sum ? shape_of(sum) : shape_of(d);
-    if (wide) QMM_TRACE(ctx, "rms_norm_vec_kernel<1024>");
-    else      QMM_TRACE(ctx, "rms_norm_vec_kernel<256>");
-    if (wide)
-        hipLaunchKernelGGL((rms_norm_vec_kernel<MUL, ADD, 1024>), dim3(rows), dim3(1024), 0, st, (const char *) a->data, b ? (const char *) b->data : nullptr,
-                           w ? (const float *) w->data : nullptr, (char *) d->data, sum ? (char *) sum->data : nullptr, shape_of(a), sb, shape_of(d), ss, eps);
-    else
-        hipLaunchKernelGGL((rms_norm_vec_kernel<MUL, ADD, 256>), dim3(rows), dim3(256), 0, st, (const char *) a->data, b ? (const char *) b->data : nullptr,
-                           w ? (const float *) w->data : nullptr, (char *) d->data, sum ? (char *) sum->data : nullptr, shape_of(a), sb, shape_of(d), ss, eps);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
-
-// y = rms_norm(a [+ b]) [* w]; `sum` receives a + b when b is given
-int launch_rms_norm(qmm_ctx * ctx, hipStream_t st, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * d, const qmm_tensor * sum, float eps) {
-    if (eps < 0.0f) return fail(QMM_EINVAL, "RMS_NORM: eps < 0");
-    const bool vec = a->ne[0] % 4 == 0 && a->ne[0] <= 1024 * 16 && aligned_to(a, 16) && aligned_to(d, 16) && (!w || (uintptr_t) w->data % 16 == 0) &&
-                     (!b || (aligned_to(b, 16) && aligned_to(sum, 16)));
-    if (vec) {
-        if (b) return w ? launch_rms_norm_vec<true, true>(ctx, st, a, b, w, d, sum, eps) : launch_rms_norm_vec<false, true>(ctx, st, a, b, w, d, sum, eps);
-        return w ? launch_rms_norm_vec<true, false>(ctx, st, a, b, w, d, sum, eps) : launch_rms_norm_vec<false, false>(ctx, st, a, b, w, d, sum, eps);
-    }
-    if (b) return fail(QMM_EUNSUPPORTED, "ADD + RMS_NORM: rows must be 16-byte aligned, ne0 %% 4 == 0 and ne0 <= 16384");
-    const dim3 grid((unsigned) nrows(d));
-    QMM_TRACE(ctx, "rms_norm_kernel");
-    if (w) hipLaunchKernelGGL((rms_norm_kernel<true>), grid, dim3(256), 0, st, (const char *) a->data, (const float *) w->data, (char *) d->data,
-                              shape_of(a), shape_of(d), eps);
-    else   hipLaunchKernelGGL((rms_norm_kernel<false>), grid, dim3(256), 0, st, (const char *) a->data, (const float *) nullptr, (char *) d->data,
-                              shape_of(a), shape_of(d), eps);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
-}
-
-float f32_param(const qmm_tensor * d, int i) {
-    float v;
-    memcpy(&v, &d->op_params[i], sizeof(float));
-    return v;
-}
+// ------------------------------------------------------------------------------------------------ host side
 
 // ggml_rope_yarn_corr_dims (ggml.c:3738-3754)
 void rope_corr_dims(int n_dims, int n_ctx_orig, float freq_base, float beta_fast, float beta_slow, float dims[2]) {
@@ -1160,319 +939,289 @@ RopeParams rope_params(const qmm_tensor * d) {
     return rp;
 }
 
-} // namespace
+// ------------------------------------------------------------------------------------------------ the executor
 
-extern "C" {
+// the operands of an entry point under their own names, and its scalar arguments
+struct GlueArgs {
+    const qmm_tensor * a = nullptr, * b = nullptr, * c = nullptr, * d = nullptr;      // qmm_op_compute: sources and destination; d: every add + norm's normed result too
+    const qmm_tensor * w = nullptr, * sum = nullptr;                                     // the weight row of a norm; the sum an add + norm also stores
+    const qmm_tensor * q = nullptr, * pos = nullptr, * ff = nullptr, * qd = nullptr, * k = nullptr, * kd = nullptr, * v = nullptr, * vd = nullptr;       // qmm_rope_kv_store
+    const qmm_tensor * gate_inp = nullptr, * logits = nullptr, * ids = nullptr, * weights = nullptr, * normed = nullptr;     // the routers; weights: the combines' too
+    const qmm_tensor * x = nullptr;                                                      // the routers' activations; the combines' expert outputs
+    float eps = 0.0f;
+    int   n_used = 0, normalise = 0;
+};
 
-int qmm_op_supported(int op, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * c, const qmm_tensor * d) {
-    if (is_binary(op)) return sup_binary(a, b, d);
-    if (is_unary(op)) return sup_unary(a, d);
-    switch (op) {
-        case QMM_OP_RMS_NORM:     return sup_rms_norm(a, d);
-        case QMM_OP_NORM:         return sup_rms_norm(a, d);
-        case QMM_OP_RMS_NORM_MUL: return sup_rms_norm(a, d) && b && b->type == G_F32 && contiguous(b) && b->ne[0] == a->ne[0] && nelements(b) == b->ne[0];
-        case QMM_OP_SILU_MUL:     return sup_unary(a, d) && b && sup_unary(b, d);
-        case QMM_OP_ROPE:         return sup_rope(a, b, c, d);
-        case QMM_OP_SOFT_MAX:     return sup_soft_max(a, b, d);
-        case QMM_OP_CPY:          return sup_cpy(a, d);
-        case QMM_OP_GET_ROWS:     return sup_get_rows(a, b, d);
-        case QMM_OP_MUL_MAT_F:    return sup_mul_mat_f(a, b, d);
-        case QMM_OP_ARGSORT:      return a && d && a->type == G_F32 && d->type == G_I32 && same_shape(a, d) && dense_rows(a) && dense_rows(d) &&
-                                         nelements(a) > 0 && a->ne[0] <= 4096 && nrows(a) < ((int64_t) 1 << 31) && (d->op_params[0] == 0 || d->op_params[0] == 1);
-        case QMM_OP_SUM_ROWS:     return a && d && a->type == G_F32 && d->type == G_F32 && dense_rows(a) && d->ne[0] == 1 && d->ne[1] == a->ne[1] &&
-                                         d->ne[2] == a->ne[2] && d->ne[3] == a->ne[3] && nelements(a) > 0 && nrows(a) < ((int64_t) 1 << 31);
-        default:                  return 0;
-    }
-}
+template <typename T> T * data_of(const qmm_tensor * t) { return t ? (T *) t->data : nullptr; }
 
-int qmm_op_add_rms_norm_supported(const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * sum, const qmm_tensor * dst) {
-    if (!a || !b || !sum || !dst || !sup_rms_norm(sum, dst) || !sup_binary(a, b, sum) || !same_shape(a, b) || !dense_rows(b)) return 0;
-    if (a->ne[0] % 4 || a->ne[0] > 1024 * 16 || a->nb[1] % 16 || a->nb[2] % 16 || a->nb[3] % 16 || b->nb[1] % 16 || b->nb[2] % 16 || b->nb[3] % 16 ||
-        sum->nb[1] % 16 || sum->nb[2] % 16 || sum->nb[3] % 16 || dst->nb[1] % 16 || dst->nb[2] % 16 || dst->nb[3] % 16) return 0;
-    if (w && !(w->type == G_F32 && contiguous(w) && w->ne[0] == a->ne[0] && nelements(w) == w->ne[0])) return 0;
-    return 1;
-}
-
-int qmm_op_compute(qmm_ctx * ctx, int op, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * c, const qmm_tensor * d, void * stream) {
-    if (!ctx || !d) return fail(QMM_EINVAL, "qmm_op_compute: NULL context or dst");
-    if (!qmm_op_supported(op, a, b, c, d)) return fail(QMM_EUNSUPPORTED, "qmm_op_compute: op %d with these types / shapes / strides is not implemented", op);
-    HIP_TRY(hipSetDevice(ctx->device));
-    QMM_CHAIN_FLUSH(ctx);
-    hipStream_t st = ctx->s(stream);
-    switch (op) {
-        case QMM_OP_ADD: return launch_binary<QMM_OP_ADD>(ctx, st, a, b, d);
-        case QMM_OP_SUB: return launch_binary<QMM_OP_SUB>(ctx, st, a, b, d);
-        case QMM_OP_MUL: return launch_binary<QMM_OP_MUL>(ctx, st, a, b, d);
-        case QMM_OP_DIV: return launch_binary<QMM_OP_DIV>(ctx, st, a, b, d);
-        case QMM_OP_SCALE:      return launch_unary<QMM_OP_SCALE, false>(ctx, st, a, nullptr, d, f32_param(d, 0));
-        case QMM_OP_SILU:       return launch_unary<QMM_OP_SILU, false>(ctx, st, a, nullptr, d, 0);
-        case QMM_OP_GELU:       return launch_unary<QMM_OP_GELU, false>(ctx, st, a, nullptr, d, 0);
-        case QMM_OP_GELU_QUICK: return launch_unary<QMM_OP_GELU_QUICK, false>(ctx, st, a, nullptr, d, 0);
-        case QMM_OP_RELU:       return launch_unary<QMM_OP_RELU, false>(ctx, st, a, nullptr, d, 0);
-        case QMM_OP_TANH:       return launch_unary<QMM_OP_TANH, false>(ctx, st, a, nullptr, d, 0);
-        case QMM_OP_SIGMOID:    return launch_unary<QMM_OP_SIGMOID, false>(ctx, st, a, nullptr, d, 0);
-        case QMM_OP_NEG:        return launch_unary<QMM_OP_NEG, false>(ctx, st, a, nullptr, d, 0);
-        case QMM_OP_EXP:        return launch_unary<QMM_OP_EXP, false>(ctx, st, a, nullptr, d, 0);
-        case QMM_OP_SILU_MUL:   return launch_unary<QMM_OP_SILU, true>(ctx, st, a, b, d, 0);
-        case QMM_OP_NORM: {
-            const float eps = f32_param(d, 0);
-            if (eps < 0.0f) return fail(QMM_EINVAL, "NORM: eps < 0");
-            QMM_TRACE(ctx, "norm_kernel");
-            hipLaunchKernelGGL(norm_kernel, dim3((unsigned) nrows(d)), dim3(256), 0, st, (const char *) a->data, (char *) d->data, shape_of(a), shape_of(d), eps);
-            HIP_TRY(hipGetLastError());
-            return QMM_OK;
+// launches a plan of qmm_glue_plan.h: the refusal, the trace label, then the one launch of the plan's kernel family with the
+// instantiation its template arguments name.  Every instantiation the library holds is named in one of the tables here
+int run_glue(qmm_ctx * ctx, hipStream_t st, const GluePlan & p, const GlueArgs & g) {
+    if (p.err) return fail(p.err, "%s", p.msg);
+    if (p.label) QMM_TRACE(ctx, p.label, p.targ[0]);
+    if (!p.launch) return QMM_OK;
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
+    const int * const t = p.targ;
+    switch (p.kernel) {
+        case GK_BINARY: {
+            static const decltype(&binary_kernel<QMM_OP_ADD, false>) K[4][2] = {
+                { binary_kernel<QMM_OP_ADD, false>, binary_kernel<QMM_OP_ADD, true> }, { binary_kernel<QMM_OP_SUB, false>, binary_kernel<QMM_OP_SUB, true> },
+                { binary_kernel<QMM_OP_MUL, false>, binary_kernel<QMM_OP_MUL, true> }, { binary_kernel<QMM_OP_DIV, false>, binary_kernel<QMM_OP_DIV, true> } };
+            hipLaunchKernelGGL((K[t[0] - QMM_OP_ADD][t[1]]), grid, block, p.lds, st, data_of<const char>(g.a), data_of<const char>(g.b), data_of<char>(g.d),
+                               shape_of(g.a), shape_of(g.b), shape_of(g.d), (uint32_t) nrows(g.d));
+            break;
         }
-        case QMM_OP_RMS_NORM:
-        case QMM_OP_RMS_NORM_MUL:
-            return launch_rms_norm(ctx, st, a, nullptr, op == QMM_OP_RMS_NORM_MUL ? b : nullptr, d, nullptr, f32_param(d, 0));
-        case QMM_OP_ROPE: {
-            const RopeParams rp = rope_params(d);
-            const uint32_t pairs = (uint32_t) (nelements(d) / 2);
-            QMM_TRACE(ctx, "rope_kernel");
-            hipLaunchKernelGGL(rope_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, (const char *) a->data, (const int32_t *) b->data,
-                               c ? (const float *) c->data : nullptr, (char *) d->data, shape_of(a), shape_of(d), rp, pairs);
-            HIP_TRY(hipGetLastError());
-            return QMM_OK;
+        case GK_UNARY: {
+            static const decltype(&unary_kernel<QMM_OP_SCALE, false>) K[9] = {
+                unary_kernel<QMM_OP_SCALE, false>, unary_kernel<QMM_OP_SILU, false>, unary_kernel<QMM_OP_GELU, false>, unary_kernel<QMM_OP_GELU_QUICK, false>,
+                unary_kernel<QMM_OP_RELU, false>, unary_kernel<QMM_OP_TANH, false>, unary_kernel<QMM_OP_SIGMOID, false>, unary_kernel<QMM_OP_NEG, false>,
+                unary_kernel<QMM_OP_EXP, false> };
+            hipLaunchKernelGGL((t[1] ? unary_kernel<QMM_OP_SILU, true> : K[t[0] - QMM_OP_SCALE]), grid, block, p.lds, st, data_of<const float>(g.a),
+                               t[1] ? data_of<const float>(g.b) : nullptr, data_of<float>(g.d), (uint32_t) nelements(g.d), t[0] == QMM_OP_SCALE ? f32_param(g.d, 0) : 0.0f);
+            break;
         }
-        case QMM_OP_SOFT_MAX: {
-            const float scale = f32_param(d, 0), max_bias = f32_param(d, 1);
-            const uint32_t nc = (uint32_t) a->ne[0], ne01 = (uint32_t) a->ne[1], ne02 = (uint32_t) a->ne[2];
-            const uint32_t n_head_log2 = 1u << (uint32_t) floor(log2((double) ne02));
+        case GK_RMS_NORM:
+            hipLaunchKernelGGL((t[0] ? rms_norm_kernel<true> : rms_norm_kernel<false>), grid, block, p.lds, st, data_of<const char>(g.a), data_of<const float>(g.w),
+                               data_of<char>(g.d), shape_of(g.a), shape_of(g.d), g.eps);
+            break;
+        case GK_RMS_NORM_VEC: {
+            static const decltype(&rms_norm_vec_kernel<false, false, 256>) K[2][2][2] = {
+                { { rms_norm_vec_kernel<false, false, 256>, rms_norm_vec_kernel<false, false, 1024> }, { rms_norm_vec_kernel<false, true, 256>, rms_norm_vec_kernel<false, true, 1024> } },
+                { { rms_norm_vec_kernel<true, false, 256>, rms_norm_vec_kernel<true, false, 1024> }, { rms_norm_vec_kernel<true, true, 256>, rms_norm_vec_kernel<true, true, 1024> } } };
+            hipLaunchKernelGGL((K[t[0]][t[1]][t[2] == 1024]), grid, block, p.lds, st, data_of<const char>(g.a), data_of<const char>(g.b), data_of<const float>(g.w),
+                               data_of<char>(g.d), data_of<char>(g.sum), shape_of(g.a), shape_of(g.b ? g.b : g.a), shape_of(g.d), shape_of(g.sum ? g.sum : g.d), g.eps);
+            break;
+        }
+        case GK_NORM:
+            hipLaunchKernelGGL((norm_kernel), grid, block, p.lds, st, data_of<const char>(g.a), data_of<char>(g.d), shape_of(g.a), shape_of(g.d), g.eps);
+            break;
+        case GK_SOFT_MAX_WAVE:
+            hipLaunchKernelGGL((t[0] == 1 ? soft_max_wave_kernel<1> : t[0] == 2 ? soft_max_wave_kernel<2> : soft_max_wave_kernel<4>), grid, block, p.lds, st,
+                               data_of<const float>(g.a), data_of<const float>(g.b), data_of<float>(g.d), (uint32_t) g.a->ne[0], (uint32_t) g.a->ne[1],
+                               (uint32_t) nrows(g.d), f32_param(g.d, 0));
+            break;
+        case GK_SOFT_MAX: {
+            const float max_bias = f32_param(g.d, 1);
+            const uint32_t n_head_log2 = 1u << (uint32_t) floor(log2((double) (uint32_t) g.a->ne[2]));
             const float m0 = powf(2.0f, -(max_bias) / n_head_log2), m1 = powf(2.0f, -(max_bias / 2.0f) / n_head_log2);
-            const size_t lds = nc <= 8192 ? (size_t) nc * 4 : 0;
-            const dim3 grid((unsigned) nrows(d));
-            const uint32_t rows = (uint32_t) nrows(d);
-            if (max_bias == 0.0f && (!b || b->type == G_F32) && nc % 4 == 0 && nc <= 1024 && rows >= 1024 && (uintptr_t) a->data % 16 == 0 &&
-                (uintptr_t) d->data % 16 == 0 && (!b || (uintptr_t) b->data % 16 == 0)) {
-                const float * m = b ? (const float *) b->data : nullptr;
-                if (nc <= 256)      QMM_TRACE(ctx, "soft_max_wave_kernel<1>");
-                else if (nc <= 512) QMM_TRACE(ctx, "soft_max_wave_kernel<2>");
-                else                QMM_TRACE(ctx, "soft_max_wave_kernel<4>");
-                if (nc <= 256)      hipLaunchKernelGGL((soft_max_wave_kernel<1>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float *) a->data, m, (float *) d->data, nc, ne01, rows, scale);
-                else if (nc <= 512) hipLaunchKernelGGL((soft_max_wave_kernel<2>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float *) a->data, m, (float *) d->data, nc, ne01, rows, scale);
-                else                hipLaunchKernelGGL((soft_max_wave_kernel<4>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float *) a->data, m, (float *) d->data, nc, ne01, rows, scale);
-                HIP_TRY(hipGetLastError());
-                return QMM_OK;
-            }
-            if (lds) QMM_TRACE(ctx, "soft_max_kernel<lds>");
-            else     QMM_TRACE(ctx, "soft_max_kernel<dst>");
-            if (b && b->type == G_F16)
-                hipLaunchKernelGGL((soft_max_kernel<true>), grid, dim3(256), lds, st, (const float *) a->data, (const void *) b->data, (float *) d->data,
-                                   nc, ne01, ne02, scale, max_bias, m0, m1, n_head_log2);
-            else
-                hipLaunchKernelGGL((soft_max_kernel<false>), grid, dim3(256), lds, st, (const float *) a->data, b ? (const void *) b->data : nullptr,
-                                   (float *) d->data, nc, ne01, ne02, scale, max_bias, m0, m1, n_head_log2);
-            HIP_TRY(hipGetLastError());
-            return QMM_OK;
+            hipLaunchKernelGGL((t[0] ? soft_max_kernel<true> : soft_max_kernel<false>), grid, block, p.lds, st, data_of<const float>(g.a), data_of<const void>(g.b),
+                               data_of<float>(g.d), (uint32_t) g.a->ne[0], (uint32_t) g.a->ne[1], (uint32_t) g.a->ne[2], f32_param(g.d, 0), max_bias, m0, m1, n_head_log2);
+            break;
         }
-        case QMM_OP_CPY: return launch_cpy(ctx, st, a, d);
-        case QMM_OP_GET_ROWS: {
-            const dim3 grid((unsigned) nrows(d));
-            if (a->type == G_F32 || a->type == G_F16) QMM_TRACE(ctx, "get_rows_kernel");
-            switch (a->type) {
-                case G_F32: hipLaunchKernelGGL((get_rows_kernel<float>), grid, dim3(256), 0, st, (const char *) a->data, (const char *) b->data,
-                                               (char *) d->data, shape_of(a), shape_of(b), shape_of(d)); break;
-                case G_F16: hipLaunchKernelGGL((get_rows_kernel<__half>), grid, dim3(256), 0, st, (const char *) a->data, (const char *) b->data,
-                                               (char *) d->data, shape_of(a), shape_of(b), shape_of(d)); break;
-                default: {
-#define QMM_X(TT) return launch_get_rows_q<TT>(ctx, st, a, b, d)
-                    QMM_FOR_TYPE(a->type, QMM_X)
+        case GK_ROPE:
+            hipLaunchKernelGGL((rope_kernel), grid, block, p.lds, st, data_of<const char>(g.a), data_of<const int32_t>(g.b), data_of<const float>(g.c), data_of<char>(g.d),
+                               shape_of(g.a), shape_of(g.d), rope_params(g.d), (uint32_t) (nelements(g.d) / 2));
+            break;
+        case GK_MEMCPY:
+            HIP_TRY(hipMemcpyAsync(g.d->data, g.a->data, (size_t) nelements(g.a) * esize(g.a->type), hipMemcpyDeviceToDevice, st));
+            return QMM_OK;
+        case GK_CPY: {
+            static const decltype(&cpy_kernel<float, float>) K[2][2] = { { cpy_kernel<float, float>, cpy_kernel<float, __half> }, { cpy_kernel<__half, float>, cpy_kernel<__half, __half> } };
+            hipLaunchKernelGGL((K[t[0] == G_F16][t[1] == G_F16]), grid, block, p.lds, st, data_of<const char>(g.a), data_of<char>(g.d), shape_of(g.a), shape_of(g.d),
+                               (uint32_t) nelements(g.a));
+            break;
+        }
+        case GK_CPY_TRANSPOSE: {
+            static const decltype(&cpy_transpose_kernel<float, float>) K[2][2] = { { cpy_transpose_kernel<float, float>, cpy_transpose_kernel<float, __half> },
+                                                                                  { cpy_transpose_kernel<__half, float>, cpy_transpose_kernel<__half, __half> } };
+            hipLaunchKernelGGL((K[t[0] == G_F16][t[1] == G_F16]), grid, block, p.lds, st, data_of<const char>(g.a), data_of<char>(g.d), (uint32_t) g.a->ne[0],
+                               (uint32_t) g.a->ne[1], g.a->nb[0], g.d->nb[1]);
+            break;
+        }
+        case GK_GET_ROWS:
+            hipLaunchKernelGGL((t[0] == G_F16 ? get_rows_kernel<__half> : get_rows_kernel<float>), grid, block, p.lds, st, data_of<const char>(g.a), data_of<const char>(g.b),
+                               data_of<char>(g.d), shape_of(g.a), shape_of(g.b), shape_of(g.d));
+            break;
+        case GK_GET_ROWS_Q: {
+            decltype(&get_rows_q_kernel<T_Q4_0>) kern;
+#define QMM_X(TT) kern = get_rows_q_kernel<TT>; break
+            QMM_FOR_TYPE(t[0], QMM_X)
 #undef QMM_X
-                }
-            }
-            HIP_TRY(hipGetLastError());
-            return QMM_OK;
+            hipLaunchKernelGGL((kern), grid, block, p.lds, st, data_of<const uint8_t>(g.a), data_of<const char>(g.b), data_of<char>(g.d), shape_of(g.a), shape_of(g.b),
+                               shape_of(g.d));
+            break;
         }
-        case QMM_OP_MUL_MAT_F: return launch_mul_mat_f(ctx, st, a, b, d);
-        case QMM_OP_ARGSORT:
-            QMM_TRACE(ctx, "argsort_kernel");
-            hipLaunchKernelGGL(argsort_kernel, dim3((unsigned) nrows(a)), dim3(256), 0, st, (const char *) a->data, (char *) d->data, shape_of(a), shape_of(d),
-                               d->op_params[0]);
-            HIP_TRY(hipGetLastError());
-            return QMM_OK;
-        case QMM_OP_SUM_ROWS: {
-            const uint32_t rows = (uint32_t) nrows(a);
-            QMM_TRACE(ctx, "sum_rows_kernel");
-            hipLaunchKernelGGL(sum_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, (const char *) a->data, (char *) d->data, shape_of(a), shape_of(d), rows);
-            HIP_TRY(hipGetLastError());
-            return QMM_OK;
+        case GK_MUL_MAT_F16:
+        case GK_MUL_MAT_DOT_BLOCK:
+        case GK_MUL_MAT_DOT: {
+            const qmm_tensor * a = g.a, * b = g.b, * d = g.d;
+            MmArgs m;
+            m.a = (const char *) a->data;  m.b = (const char *) b->data;  m.d = (char *) d->data;
+            m.a_nb1 = a->nb[1]; m.a_nb2 = a->nb[2]; m.a_nb3 = a->nb[3];
+            m.b_nb1 = b->nb[1]; m.b_nb2 = b->nb[2]; m.b_nb3 = b->nb[3];
+            m.d_nb1 = d->nb[1]; m.d_nb2 = d->nb[2]; m.d_nb3 = d->nb[3];
+            m.M = (int32_t) a->ne[1]; m.N = (int32_t) b->ne[1]; m.K = (int32_t) a->ne[0];
+            m.ne12 = (int32_t) b->ne[2]; m.r2 = (int32_t) (b->ne[2] / a->ne[2]); m.r3 = (int32_t) (b->ne[3] / a->ne[3]);
+            hipLaunchKernelGGL((p.kernel == GK_MUL_MAT_DOT_BLOCK ? mul_mat_dot_block_kernel : p.kernel == GK_MUL_MAT_DOT ? mul_mat_dot_kernel<float> :
+                               t[0] ? mul_mat_f16_kernel<true> : mul_mat_f16_kernel<false>), grid, block, p.lds, st, m);
+            break;
         }
-        default: return fail(QMM_EUNSUPPORTED, "qmm_op_compute: unknown op %d", op);
-    }
-}
-
-int qmm_op_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * sum,
-                        const qmm_tensor * dst, float eps, void * stream) {
-    if (!ctx || !qmm_op_add_rms_norm_supported(a, b, w, sum, dst)) return fail(QMM_EUNSUPPORTED, "qmm_op_add_rms_norm: operands not supported");
-    HIP_TRY(hipSetDevice(ctx->device));
-    QMM_CHAIN_FLUSH(ctx);
-    return launch_rms_norm(ctx, ctx->s(stream), a, b, w, dst, sum, eps);
-}
-
-int qmm_rope_kv_store_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
-                                const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst) {
-    if (!sup_rope(q, pos, ff, q_dst)) return 0;
-    if (k) {
-        if (!k_dst || k->type != G_F32 || k_dst->type != G_F16 || !same_shape(k, k_dst) || !dense_rows(k) || !dense_rows(k_dst) || !fits_u32(k)) return 0;
-        if (k->ne[0] != q->ne[0] || k->ne[2] != q->ne[2] || k->ne[3] != q->ne[3] || nelements(k) == 0) return 0;
-        if (k->nb[1] % 4 || k->nb[2] % 4 || k->nb[3] % 4 || k_dst->nb[1] % 2 || k_dst->nb[2] % 2 || k_dst->nb[3] % 2) return 0;
-    }
-    if (v) {
-        if (!v_dst || v->type != G_F32 || v_dst->type != G_F16 || nelements(v) != nelements(v_dst) || !fits_u32(v) || nelements(v) == 0) return 0;
-        if (v->nb[0] % 4 || v->nb[1] % 4 || v->nb[2] % 4 || v->nb[3] % 4 || v_dst->nb[0] % 2 || v_dst->nb[1] % 2 || v_dst->nb[2] % 2 || v_dst->nb[3] % 2) return 0;
-    }
-    return nelements(q) / 2 + (k ? nelements(k) / 2 : 0) + (v ? nelements(v) : 0) < ((int64_t) 1 << 31);
-}
-
-int qmm_rope_kv_store(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
-                      const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst, void * stream) {
-    if (!ctx || !qmm_rope_kv_store_supported(q, pos, ff, q_dst, k, k_dst, v, v_dst)) return fail(QMM_EUNSUPPORTED, "qmm_rope_kv_store: operands not supported");
-    HIP_TRY(hipSetDevice(ctx->device));
-    QMM_CHAIN_FLUSH(ctx);
-    RopeStoreArgs g;
-    g.q = (const char *) q->data; g.qd = (char *) q_dst->data; g.sq = shape_of(q); g.sqd = shape_of(q_dst);
-    g.k = k ? (const char *) k->data : nullptr; g.kd = k ? (char *) k_dst->data : nullptr; g.sk = shape_of(k ? k : q); g.skd = shape_of(k ? k_dst : q_dst);
-    g.v = v ? (const char *) v->data : nullptr; g.vd = v ? (char *) v_dst->data : nullptr; g.sv = shape_of(v ? v : q); g.svd = shape_of(v ? v_dst : q_dst);
-    g.pos = (const int32_t *) pos->data; g.ff = ff ? (const float *) ff->data : nullptr;
-    g.rp = rope_params(q_dst);
-    g.nq = rope_heads_threads(g.sq); g.nk = k ? rope_heads_threads(g.sk) : 0; g.nv = v ? (uint32_t) nelements(v) : 0;
-    const bool vt = v && v->ne[2] == 1 && v->ne[3] == 1 && v_dst->ne[2] == 1 && v_dst->ne[3] == 1 && v->ne[0] == v_dst->ne[0] && v->ne[1] == v_dst->ne[1] &&
-                    v->nb[1] == 4 && v_dst->nb[0] == 2 && v->ne[0] >= 32 && v->ne[1] >= 32;
-    if (vt) {
-        const uint32_t pair_blocks = (g.nq + g.nk + 255) / 256, tiles0 = (uint32_t) ((v->ne[0] + 31) / 32), tiles1 = (uint32_t) ((v->ne[1] + 31) / 32);
-        hipLaunchKernelGGL((rope_store_kernel<true>), dim3(pair_blocks + tiles0 * tiles1), dim3(256), 0, ctx->s(stream), g, pair_blocks, tiles0);
-    } else {
-        const uint32_t total = g.nq + g.nk + g.nv;
-        hipLaunchKernelGGL((rope_store_kernel<false>), dim3((total + 255) / 256), dim3(256), 0, ctx->s(stream), g, 0u, 0u);
+        case GK_ARGSORT:
+            hipLaunchKernelGGL((argsort_kernel), grid, block, p.lds, st, data_of<const char>(g.a), data_of<char>(g.d), shape_of(g.a), shape_of(g.d), g.d->op_params[0]);
+            break;
+        case GK_SUM_ROWS:
+            hipLaunchKernelGGL((sum_rows_kernel), grid, block, p.lds, st, data_of<const char>(g.a), data_of<char>(g.d), shape_of(g.a), shape_of(g.d), (uint32_t) nrows(g.a));
+            break;
+        case GK_ROPE_STORE: {
+            RopeStoreArgs r;
+            r.q = data_of<const char>(g.q); r.qd = data_of<char>(g.qd); r.sq = shape_of(g.q); r.sqd = shape_of(g.qd);
+            r.k = data_of<const char>(g.k); r.kd = data_of<char>(g.k ? g.kd : nullptr); r.sk = shape_of(g.k ? g.k : g.q); r.skd = shape_of(g.k ? g.kd : g.qd);
+            r.v = data_of<const char>(g.v); r.vd = data_of<char>(g.v ? g.vd : nullptr); r.sv = shape_of(g.v ? g.v : g.q); r.svd = shape_of(g.v ? g.vd : g.qd);
+            r.pos = data_of<const int32_t>(g.pos); r.ff = data_of<const float>(g.ff);
+            r.rp = rope_params(g.qd);
+            r.nq = rope_heads_threads(g.q); r.nk = g.k ? rope_heads_threads(g.k) : 0; r.nv = g.v ? (uint32_t) nelements(g.v) : 0;
+            hipLaunchKernelGGL((t[0] ? rope_store_kernel<true> : rope_store_kernel<false>), grid, block, p.lds, st, r, p.karg[0], p.karg[1]);
+            break;
+        }
+        case GK_MOE_ROUTER:
+            hipLaunchKernelGGL((moe_router_kernel), grid, block, p.lds, st, data_of<const char>(g.logits), data_of<char>(g.ids), data_of<char>(g.weights), g.logits->nb[1], g.ids->nb[1],
+                               (int64_t) g.n_used * 4, (int) g.logits->ne[0], g.n_used, (int) g.logits->ne[1], g.normalise);
+            break;
+        case GK_MOE_ROUTER_LOGITS:
+            hipLaunchKernelGGL((t[0] ? moe_router_logits_kernel<true> : moe_router_logits_kernel<false>), grid, block, p.lds, st, data_of<const char>(g.gate_inp), data_of<const char>(g.x),
+                               data_of<char>(g.logits), data_of<char>(g.ids), data_of<char>(g.weights), g.gate_inp->nb[1], g.x->nb[1], g.logits->nb[1], g.ids->nb[1], (int64_t) g.n_used * 4,
+                               (int) g.gate_inp->ne[0], (int) g.logits->ne[0], g.n_used, g.normalise, data_of<const float>(g.w), g.eps, data_of<char>(g.normed), g.normed ? g.normed->nb[1] : (int64_t) 0);
+            break;
+        case GK_MOE_COMBINE:
+            hipLaunchKernelGGL((moe_combine_kernel), grid, block, p.lds, st, data_of<const char>(g.x), data_of<const char>(g.weights), data_of<char>(g.d), g.x->nb[1], g.x->nb[2],
+                               g.weights->nb[1], g.weights->nb[2], g.d->nb[1], (int) g.x->ne[0], (int) g.x->ne[1]);
+            break;
+        case GK_MOE_COMBINE_ADD_NORM:
+            hipLaunchKernelGGL((t[0] == 1024 ? moe_combine_add_norm_kernel<1024> : moe_combine_add_norm_kernel<256>), grid, block, p.lds, st, data_of<const char>(g.x),
+                               data_of<const char>(g.weights), data_of<const char>(g.b), data_of<const float>(g.w), data_of<char>(g.d), data_of<char>(g.sum), g.x->nb[1], g.x->nb[2],
+                               g.weights->nb[1], g.weights->nb[2], g.b->nb[1], g.d->nb[1], g.sum->nb[1], (int) g.x->ne[0], (int) g.x->ne[1], g.eps);
+            break;
+        default: return fail(QMM_EUNSUPPORTED, "glue ops: no kernel for plan %d", p.kernel);
     }
     HIP_TRY(hipGetLastError());
     return QMM_OK;
 }
 
-} // extern "C"
+} // namespace
 
 #include "qmm_attn.hiph"         // the attention kernels, their launch executor and entry points
 
 extern "C" {
 
+int qmm_op_supported(int op, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * c, const qmm_tensor * d) { return sup_op(op, a, b, c, d); }
+
+int qmm_op_compute(qmm_ctx * ctx, int op, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * c, const qmm_tensor * d, void * stream) {
+    if (!ctx || !d) return fail(QMM_EINVAL, "qmm_op_compute: NULL context or dst");
+    if (!sup_op(op, a, b, c, d)) return fail(QMM_EUNSUPPORTED, "qmm_op_compute: op %d with these types / shapes / strides is not implemented", op);
+    HIP_TRY(hipSetDevice(ctx->device));
+    QMM_CHAIN_FLUSH(ctx);
+    GlueArgs g;
+    g.a = a; g.b = b; g.c = c; g.d = d;
+    if (op == QMM_OP_NORM || op == QMM_OP_RMS_NORM || op == QMM_OP_RMS_NORM_MUL) {
+        g.eps = f32_param(d, 0);
+        if (g.eps < 0.0f) return fail(QMM_EINVAL, op == QMM_OP_NORM ? "NORM: eps < 0" : "RMS_NORM: eps < 0");
+        g.w = op == QMM_OP_RMS_NORM_MUL ? b : nullptr;
+        g.b = nullptr;
+    }
+    return run_glue(ctx, ctx->s(stream), glue_op_plan(op, a, b, c, d), g);
+}
+
+int qmm_op_add_rms_norm_supported(const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * sum, const qmm_tensor * dst) {
+    return sup_add_rms_norm(a, b, w, sum, dst);
+}
+
+int qmm_op_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * w, const qmm_tensor * sum,
+                        const qmm_tensor * dst, float eps, void * stream) {
+    if (!ctx || !sup_add_rms_norm(a, b, w, sum, dst)) return fail(QMM_EUNSUPPORTED, "qmm_op_add_rms_norm: operands not supported");
+    HIP_TRY(hipSetDevice(ctx->device));
+    QMM_CHAIN_FLUSH(ctx);
+    if (eps < 0.0f) return fail(QMM_EINVAL, "RMS_NORM: eps < 0");
+    GlueArgs g;
+    g.a = a; g.b = b; g.w = w; g.sum = sum; g.d = dst; g.eps = eps;
+    return run_glue(ctx, ctx->s(stream), glue_add_rms_norm_plan(a, b, w, sum, dst), g);
+}
+
+int qmm_rope_kv_store_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
+                                const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst) {
+    return sup_rope_kv_store(q, pos, ff, q_dst, k, k_dst, v, v_dst);
+}
+
+int qmm_rope_kv_store(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
+                      const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst, void * stream) {
+    if (!ctx || !sup_rope_kv_store(q, pos, ff, q_dst, k, k_dst, v, v_dst)) return fail(QMM_EUNSUPPORTED, "qmm_rope_kv_store: operands not supported");
+    HIP_TRY(hipSetDevice(ctx->device));
+    QMM_CHAIN_FLUSH(ctx);
+    GlueArgs g;
+    g.q = q; g.pos = pos; g.ff = ff; g.qd = q_dst; g.k = k; g.kd = k_dst; g.v = v; g.vd = v_dst;
+    return run_glue(ctx, ctx->s(stream), glue_rope_kv_store_plan(q, k, v, v_dst), g);
+}
+
 int qmm_moe_router_supported(const qmm_tensor * logits, const qmm_tensor * ids, const qmm_tensor * weights, int64_t n_used) {
-    if (!logits || !ids || !weights || logits->type != G_F32 || ids->type != G_I32 || weights->type != G_F32) return 0;
-    const int64_t E = logits->ne[0], N = logits->ne[1];
-    if (E < 1 || E > 64 || n_used < 1 || n_used > E || N < 1 || N >= ((int64_t) 1 << 30)) return 0;
-    if (logits->ne[2] != 1 || logits->ne[3] != 1 || ids->ne[0] != E || ids->ne[1] != N || ids->ne[2] != 1 || ids->ne[3] != 1) return 0;
-    if (weights->ne[0] * weights->ne[1] * weights->ne[2] * weights->ne[3] != n_used * N) return 0;
-    return logits->nb[0] == 4 && ids->nb[0] == 4 && weights->nb[0] == 4 && logits->nb[1] % 4 == 0 && ids->nb[1] % 4 == 0;
+    return sup_moe_router(logits, ids, weights, n_used);
 }
 
 int qmm_moe_router(qmm_ctx * ctx, const qmm_tensor * logits, const qmm_tensor * ids, const qmm_tensor * weights, int64_t n_used, int normalise,
                    void * stream) {
-    if (!ctx || !qmm_moe_router_supported(logits, ids, weights, n_used)) return fail(QMM_EUNSUPPORTED, "qmm_moe_router: operands not supported");
+    if (!ctx || !sup_moe_router(logits, ids, weights, n_used)) return fail(QMM_EUNSUPPORTED, "qmm_moe_router: operands not supported");
     HIP_TRY(hipSetDevice(ctx->device));
     QMM_CHAIN_FLUSH(ctx);
-    const int N = (int) logits->ne[1];
-    hipLaunchKernelGGL(moe_router_kernel, dim3((N + 3) / 4), dim3(256), 0, ctx->s(stream), (const char *) logits->data, (char *) ids->data,
-                       (char *) weights->data, logits->nb[1], ids->nb[1], (int64_t) n_used * 4, (int) logits->ne[0], (int) n_used, N, normalise);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
+    GlueArgs g;
+    g.logits = logits; g.ids = ids; g.weights = weights; g.n_used = (int) n_used; g.normalise = normalise;
+    return run_glue(ctx, ctx->s(stream), glue_moe_router_plan(logits), g);
 }
 
 int qmm_moe_router_logits_supported(const qmm_tensor * gate_inp, const qmm_tensor * x, const qmm_tensor * logits, const qmm_tensor * ids,
                                     const qmm_tensor * weights, int64_t n_used) {
-    if (!gate_inp || !x || !qmm_moe_router_supported(logits, ids, weights, n_used)) return 0;
-    if (gate_inp->type != G_F32 || x->type != G_F32) return 0;
-    const int64_t K = gate_inp->ne[0], E = gate_inp->ne[1], N = x->ne[1];
-    // (more tokens: the tiled MUL_MAT + moe_router_kernel; K < 1024: qmm_op(MUL_MAT) takes a wave per element there, another order of additions)
-    if (K < 1024 || K >= ((int64_t) 1 << 30) || E != logits->ne[0] || N != logits->ne[1] || N > 8 || x->ne[0] != K) return 0;
-    if (gate_inp->ne[2] != 1 || gate_inp->ne[3] != 1 || x->ne[2] != 1 || x->ne[3] != 1) return 0;
-    return gate_inp->nb[0] == 4 && x->nb[0] == 4 && gate_inp->nb[1] % 4 == 0 && x->nb[1] % 4 == 0;
+    return sup_moe_router_logits(gate_inp, x, logits, ids, weights, n_used);
 }
 
 int qmm_moe_router_logits(qmm_ctx * ctx, const qmm_tensor * gate_inp, const qmm_tensor * x, const qmm_tensor * logits, const qmm_tensor * ids,
                           const qmm_tensor * weights, int64_t n_used, int normalise, void * stream) {
-    if (!ctx || !qmm_moe_router_logits_supported(gate_inp, x, logits, ids, weights, n_used))
+    if (!ctx || !sup_moe_router_logits(gate_inp, x, logits, ids, weights, n_used))
         return fail(QMM_EUNSUPPORTED, "qmm_moe_router_logits: operands not supported");
     HIP_TRY(hipSetDevice(ctx->device));
     QMM_CHAIN_FLUSH(ctx);
-    hipLaunchKernelGGL(moe_router_logits_kernel<false>, dim3((unsigned) x->ne[1]), dim3(1024), 0, ctx->s(stream), (const char *) gate_inp->data, (const char *) x->data,
-                       (char *) logits->data, (char *) ids->data, (char *) weights->data, gate_inp->nb[1], x->nb[1], logits->nb[1], ids->nb[1], (int64_t) n_used * 4,
-                       (int) gate_inp->ne[0], (int) logits->ne[0], (int) n_used, normalise, nullptr, 0.0f, nullptr, 0);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
+    GlueArgs g;
+    g.gate_inp = gate_inp; g.x = x; g.logits = logits; g.ids = ids; g.weights = weights; g.n_used = (int) n_used; g.normalise = normalise;
+    return run_glue(ctx, ctx->s(stream), glue_moe_router_logits_plan(x, false), g);
 }
 
 int qmm_moe_router_logits_norm_supported(const qmm_tensor * gate_inp, const qmm_tensor * x, const qmm_tensor * norm_w, const qmm_tensor * normed,
                                          const qmm_tensor * logits, const qmm_tensor * ids, const qmm_tensor * weights, int64_t n_used) {
-    if (!norm_w || !normed || !qmm_moe_router_logits_supported(gate_inp, x, logits, ids, weights, n_used)) return 0;
-    const int64_t K = x->ne[0];
-    if (norm_w->type != G_F32 || normed->type != G_F32 || K % 4 || K > 16384) return 0;
-    if (norm_w->ne[0] != K || norm_w->ne[1] * norm_w->ne[2] * norm_w->ne[3] != 1 || norm_w->nb[0] != 4) return 0;
-    for (int i = 0; i < 4; ++i) if (normed->ne[i] != x->ne[i]) return 0;
-    if (normed->nb[0] != 4 || x->nb[1] % 16 || normed->nb[1] % 16 || gate_inp->nb[1] % 16) return 0;
-    return (uintptr_t) x->data % 16 == 0 && (uintptr_t) normed->data % 16 == 0 && (uintptr_t) norm_w->data % 16 == 0 && (uintptr_t) gate_inp->data % 16 == 0;
+    return sup_moe_router_logits_norm(gate_inp, x, norm_w, normed, logits, ids, weights, n_used);
 }
 
 int qmm_moe_router_logits_norm(qmm_ctx * ctx, const qmm_tensor * gate_inp, const qmm_tensor * x, const qmm_tensor * norm_w, float eps, const qmm_tensor * normed,
                                const qmm_tensor * logits, const qmm_tensor * ids, const qmm_tensor * weights, int64_t n_used, int normalise, void * stream) {
-    if (!ctx || eps < 0.0f || !qmm_moe_router_logits_norm_supported(gate_inp, x, norm_w, normed, logits, ids, weights, n_used))
+    if (!ctx || eps < 0.0f || !sup_moe_router_logits_norm(gate_inp, x, norm_w, normed, logits, ids, weights, n_used))
         return fail(QMM_EUNSUPPORTED, "qmm_moe_router_logits_norm: operands not supported");
     HIP_TRY(hipSetDevice(ctx->device));
     QMM_CHAIN_FLUSH(ctx);
-    hipLaunchKernelGGL(moe_router_logits_kernel<true>, dim3((unsigned) x->ne[1]), dim3(1024), (size_t) x->ne[0] * 4, ctx->s(stream), (const char *) gate_inp->data,
-                       (const char *) x->data, (char *) logits->data, (char *) ids->data, (char *) weights->data, gate_inp->nb[1], x->nb[1], logits->nb[1], ids->nb[1],
-                       (int64_t) n_used * 4, (int) gate_inp->ne[0], (int) logits->ne[0], (int) n_used, normalise, (const float *) norm_w->data, eps,
-                       (char *) normed->data, normed->nb[1]);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
+    GlueArgs g;
+    g.gate_inp = gate_inp; g.x = x; g.logits = logits; g.normed = normed; g.w = norm_w; g.eps = eps; g.ids = ids; g.weights = weights; g.n_used = (int) n_used; g.normalise = normalise;
+    return run_glue(ctx, ctx->s(stream), glue_moe_router_logits_plan(x, true), g);
 }
 
-int qmm_moe_combine_supported(const qmm_tensor * x, const qmm_tensor * w, const qmm_tensor * out) {
-    if (!x || !w || !out || x->type != G_F32 || w->type != G_F32 || out->type != G_F32) return 0;
-    const int64_t E = x->ne[0], U = x->ne[1], N = x->ne[2];
-    if (E < 4 || E % 4 || U < 1 || U > 64 || N < 1 || N > 65535 || x->ne[3] != 1) return 0;
-    if (w->ne[0] != 1 || w->ne[1] != U || w->ne[2] != N || w->ne[3] != 1 || out->ne[0] != E || out->ne[1] != N || out->ne[2] != 1 || out->ne[3] != 1) return 0;
-    if (x->nb[0] != 4 || out->nb[0] != 4 || x->nb[1] % 16 || x->nb[2] % 16 || out->nb[1] % 16 || w->nb[1] % 4 || w->nb[2] % 4) return 0;
-    return 1;
-}
+int qmm_moe_combine_supported(const qmm_tensor * x, const qmm_tensor * w, const qmm_tensor * out) { return sup_moe_combine(x, w, out); }
 
 int qmm_moe_combine(qmm_ctx * ctx, const qmm_tensor * x, const qmm_tensor * w, const qmm_tensor * out, void * stream) {
-    if (!ctx || !qmm_moe_combine_supported(x, w, out)) return fail(QMM_EUNSUPPORTED, "qmm_moe_combine: operands not supported");
-    if ((uintptr_t) x->data % 16 || (uintptr_t) out->data % 16) return fail(QMM_EINVAL, "qmm_moe_combine: x / out must be 16-byte aligned");
+    if (!ctx || !sup_moe_combine(x, w, out)) return fail(QMM_EUNSUPPORTED, "qmm_moe_combine: operands not supported");
     HIP_TRY(hipSetDevice(ctx->device));
     QMM_CHAIN_FLUSH(ctx);
-    const int E = (int) x->ne[0];
-    hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned) ((E / 4 + 255) / 256), (unsigned) x->ne[2]), dim3(256), 0, ctx->s(stream), (const char *) x->data,
-                       (const char *) w->data, (char *) out->data, x->nb[1], x->nb[2], w->nb[1], w->nb[2], out->nb[1], E, (int) x->ne[1]);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
+    GlueArgs g;
+    g.x = x; g.weights = w; g.d = out;
+    return run_glue(ctx, ctx->s(stream), glue_moe_combine_plan(x, out), g);
 }
 
 int qmm_moe_combine_add_rms_norm_supported(const qmm_tensor * x, const qmm_tensor * w, const qmm_tensor * b, const qmm_tensor * nw, const qmm_tensor * sum,
                                            const qmm_tensor * dst) {
-    if (!b || !nw || !sum || !dst || !qmm_moe_combine_supported(x, w, sum)) return 0;
-    const int64_t E = x->ne[0], N = x->ne[2];
-    if (E > 1024 * 16 || b->type != G_F32 || nw->type != G_F32 || dst->type != G_F32) return 0;
-    for (const qmm_tensor * t : { b, sum, dst })
-        if (t->ne[0] != E || t->ne[1] != N || t->ne[2] != 1 || t->ne[3] != 1 || t->nb[0] != 4 || t->nb[1] % 16 || (uintptr_t) t->data % 16) return 0;
-    return nw->ne[0] == E && nw->ne[1] * nw->ne[2] * nw->ne[3] == 1 && nw->nb[0] == 4 && (uintptr_t) nw->data % 16 == 0 && (uintptr_t) x->data % 16 == 0;
+    return sup_moe_combine_add_rms_norm(x, w, b, nw, sum, dst);
 }
 
 int qmm_moe_combine_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * x, const qmm_tensor * w, const qmm_tensor * b, const qmm_tensor * nw, const qmm_tensor * sum,
                                  const qmm_tensor * dst, float eps, void * stream) {
-    if (!ctx || !qmm_moe_combine_add_rms_norm_supported(x, w, b, nw, sum, dst)) return fail(QMM_EUNSUPPORTED, "qmm_moe_combine_add_rms_norm: operands not supported");
+    if (!ctx || !sup_moe_combine_add_rms_norm(x, w, b, nw, sum, dst)) return fail(QMM_EUNSUPPORTED, "qmm_moe_combine_add_rms_norm: operands not supported");
     if (eps < 0.0f) return fail(QMM_EINVAL, "qmm_moe_combine_add_rms_norm: eps < 0");
     HIP_TRY(hipSetDevice(ctx->device));
     QMM_CHAIN_FLUSH(ctx);
-    const int E = (int) x->ne[0], N = (int) x->ne[2];
-    const bool wide = N < 256 || E > 256 * 16;              // launch_rms_norm_vec's rule: the same partition as the stand-alone kernel
-    hipStream_t st = ctx->s(stream);
-    if (wide) hipLaunchKernelGGL((moe_combine_add_norm_kernel<1024>), dim3((unsigned) N), dim3(1024), 0, st, (const char *) x->data, (const char *) w->data, (const char *) b->data,
-                                 (const float *) nw->data, (char *) dst->data, (char *) sum->data, x->nb[1], x->nb[2], w->nb[1], w->nb[2], b->nb[1], dst->nb[1], sum->nb[1], E,
-                                 (int) x->ne[1], eps);
-    else      hipLaunchKernelGGL((moe_combine_add_norm_kernel<256>), dim3((unsigned) N), dim3(256), 0, st, (const char *) x->data, (const char *) w->data, (const char *) b->data,
-                                 (const float *) nw->data, (char *) dst->data, (char *) sum->data, x->nb[1], x->nb[2], w->nb[1], w->nb[2], b->nb[1], dst->nb[1], sum->nb[1], E,
-                                 (int) x->ne[1], eps);
-    HIP_TRY(hipGetLastError());
-    return QMM_OK;
+    GlueArgs g;
+    g.x = x; g.weights = w; g.b = b; g.w = nw; g.sum = sum; g.d = dst; g.eps = eps;
+    return run_glue(ctx, ctx->s(stream), glue_moe_combine_add_rms_norm_plan(x), g);
 }
 
 } // extern "C"

@@ -1,4 +1,4 @@
-"""The cases of tests/test_gpu_glue_ops.py: for every launcher branch of csrc/qmm_ops.hip the smallest operands that reach it.
+"""The cases of tests/test_gpu_glue_ops.py: for every branch of the launch plan csrc/qmm_glue_plan.h the smallest operands that reach it.
 Each case is built on the CPU (operands as glue_refs.Buf, the float64 reference, the float32 restatement, the trace label it must
 take); tests/test_glue_refs.py checks the restatements on the CPU, tests/test_gpu_glue_ops.py runs the kernels.  A plain module."""
 import zlib

@@ -1,6 +1,6 @@
 """The numpy references of tests/glue_refs.py against independent implementations (torch on the CPU, properties written out by hand),
 so that a shared misunderstanding between a reference and its kernel cannot hide; the float32 restatements of every GPU case against
-their float64 references; and the trace labels of csrc/qmm_ops.hip against the cases, so that a new launcher branch cannot arrive
+their float64 references; and the trace labels of csrc/qmm_glue_plan.h against the cases, so that a new launcher branch cannot arrive
 untested.  No GPU."""
 import re
 from pathlib import Path
@@ -217,9 +217,15 @@ def test_no_case_has_a_fully_masked_row_or_a_nan():
 
 # ------------------------------------------------------------------------------------------------ labels
 def glue_labels():
-    """the label strings of every QMM_TRACE in csrc/qmm_ops.hip; a %d stands for a template argument"""
-    src = (ROOT / "ggml-hexagon_amd" / "csrc" / "qmm_ops.hip").read_text()
-    return sorted(set(re.findall(r'QMM_TRACE\(\s*\w+\s*,\s*"([^"]+)"', src)))
+    """the label strings of the one table of csrc/qmm_glue_plan.h (GLUE_LABELS) that every glue plan takes its label from; a %d stands for a
+    template argument"""
+    src = (ROOT / "ggml-hexagon_amd" / "csrc" / "qmm_glue_plan.h").read_text()
+    table = re.search(r"GLUE_LABELS\[GL_COUNT\]\s*=\s*\{(.*?)\};", src, re.S).group(1)
+    labels = re.findall(r'"([^"]+)"', table)
+    assert len(labels) == len(set(labels))
+    rest = re.sub(r"GLUE_LABELS\[GL_COUNT\]\s*=\s*\{.*?\};", "", src, flags=re.S)
+    assert not [t for t in re.findall(r'"([^"]+)"', rest) if "_kernel" in t or t == "memcpy"]          # no label is spelled outside the table
+    return sorted(labels)
 
 
 def test_every_trace_label_of_the_glue_launchers_has_a_case():

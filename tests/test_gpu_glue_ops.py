@@ -23,7 +23,7 @@ import glue_refs as R  # noqa: E402
 from glue_refs import F32, I32, Buf  # noqa: E402
 from oracle.pyoracle import TYPE_NAMES, WEIGHT_TYPES  # noqa: E402
 
-# every label the glue launchers can emit (tests/test_glue_refs.py holds this list against the QMM_TRACE calls of qmm_ops.hip and
+# every label the glue launches can emit (tests/test_glue_refs.py holds this list against the label table of qmm_glue_plan.h and
 # against the labels the cases assert)
 LABELS = ("binary_kernel<vec>", "binary_kernel<scalar>", "unary_kernel", "rms_norm_vec_kernel<1024>", "rms_norm_vec_kernel<256>", "rms_norm_kernel",
           "norm_kernel", "soft_max_wave_kernel<1>", "soft_max_wave_kernel<2>", "soft_max_wave_kernel<4>", "soft_max_kernel<lds>", "soft_max_kernel<dst>",

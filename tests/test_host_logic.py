@@ -1115,3 +1115,519 @@ def test_attn_rules_live_in_one_place():
     for n, line in enumerate(code_of(dev), 1):
         assert not re.search(r"n_kv\s*<=", line), f"{dev.name}:{n}: {line.strip()[:120]}"
     assert any("attn_decode_plan" in line for line in code_of(dev))
+
+
+# ---- the glue launch plan (csrc/qmm_glue_plan.h): for the operands of an entry point the kernel, its instantiation, grid, block, LDS, label, refusal
+
+GLUE_PLAN_HEADER = ROOT / "ggml-hexagon_amd" / "csrc" / "qmm_glue_plan.h"
+GLUE_UNIT = ROOT / "ggml-hexagon_amd" / "csrc" / "qmm_ops.hip"
+GLUE_PLAN_PROBE = r"""
+#include "qmm_glue_plan.h"
+// one operand spec per line:  ENTRY [n_used=N] [pi<i>=INT] [pf<i>=FLOAT] NAME=TYPE:ne0[,ne1[,ne2[,ne3]]][/nb0,nb1,nb2,nb3][@ADDRESS] ...
+// TYPE f32 | f16 | i32 | t<ggml type id>; strides default to contiguous; the data pointer to a 1 MiB slot of its own; pi / pf set
+// op_params of the tensor named d (qd for rope_store)
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <map>
+#include <sstream>
+#include <string>
+struct Spec {
+    std::string entry;
+    std::map<std::string, qmm_tensor> t;
+    long n_used = 2;
+    const qmm_tensor * get(const char * name) const { auto it = t.find(name); return it == t.end() ? nullptr : &it->second; }
+};
+static bool parse_spec(const std::string & line, Spec & s) {
+    std::istringstream in(line);
+    std::string tok;
+    if (!(in >> s.entry)) return false;
+    int slot = 0, pi[16] = {0};
+    bool pset[16] = {false};
+    while (in >> tok) {
+        const size_t eq = tok.find('=');
+        if (eq == std::string::npos) return false;
+        const std::string name = tok.substr(0, eq), val = tok.substr(eq + 1);
+        if (name == "n_used") { s.n_used = atol(val.c_str()); continue; }
+        if (name.size() >= 3 && name[0] == 'p' && (name[1] == 'i' || name[1] == 'f') && isdigit(name[2])) {
+            const int i = atoi(name.c_str() + 2);
+            if (name[1] == 'i') pi[i] = atoi(val.c_str());
+            else { const float f = (float) atof(val.c_str()); memcpy(&pi[i], &f, 4); }
+            pset[i] = true;
+            continue;
+        }
+        qmm_tensor q;
+        memset(&q, 0, sizeof(q));
+        const size_t colon = val.find(':');
+        if (colon == std::string::npos) return false;
+        const std::string ty = val.substr(0, colon);
+        q.type = ty == "f32" ? 0 : ty == "f16" ? 1 : ty == "i32" ? 26 : ty[0] == 't' ? atoi(ty.c_str() + 1) : -1;
+        if (q.type < 0) return false;
+        std::string rest = val.substr(colon + 1), addr, nb;
+        size_t at = rest.find('@');
+        if (at != std::string::npos) { addr = rest.substr(at + 1); rest = rest.substr(0, at); }
+        size_t sl = rest.find('/');
+        if (sl != std::string::npos) { nb = rest.substr(sl + 1); rest = rest.substr(0, sl); }
+        for (int i = 0; i < 4; ++i) q.ne[i] = 1;
+        { std::istringstream e(rest); std::string x; int i = 0; while (std::getline(e, x, ',') && i < 4) q.ne[i++] = atoll(x.c_str()); }
+        const bool quant = q.type != 0 && q.type != 1 && q.type != 26;
+        q.nb[0] = quant ? qmm::type_tsize(q.type) : q.type == 1 ? 2 : 4;
+        q.nb[1] = quant ? q.ne[0] / qmm::type_blck(q.type) * q.nb[0] : q.nb[0] * q.ne[0];
+        q.nb[2] = q.nb[1] * q.ne[1];
+        q.nb[3] = q.nb[2] * q.ne[2];
+        if (!nb.empty()) { std::istringstream e(nb); std::string x; int i = 0; while (std::getline(e, x, ',') && i < 4) q.nb[i++] = atoll(x.c_str()); }
+        q.data = (void *) (uintptr_t) (addr.empty() ? (uint64_t) (++slot) << 20 : strtoull(addr.c_str(), nullptr, 0));
+        if (addr.empty() == false) ++slot;
+        s.t[name] = q;
+    }
+    for (const char * dn : { "d", "qd" }) {
+        auto it = s.t.find(dn);
+        if (it != s.t.end()) for (int i = 0; i < 16; ++i) if (pset[i]) it->second.op_params[i] = pi[i];
+    }
+    return true;
+}
+static int op_id(const std::string & n) {
+    static const char * names[] = { "", "ADD", "SUB", "MUL", "DIV", "SCALE", "SILU", "GELU", "GELU_QUICK", "RELU", "TANH", "SIGMOID", "NEG", "EXP", "RMS_NORM", "ROPE",
+                                    "SOFT_MAX", "CPY", "GET_ROWS", "MUL_MAT_F", "RMS_NORM_MUL", "SILU_MUL", "ARGSORT", "SUM_ROWS", "NORM" };
+    for (int i = 1; i < (int) (sizeof(names) / sizeof(names[0])); ++i) if (n == names[i]) return i;
+    return 0;
+}
+using namespace qmm;
+int main() {
+    static const struct { const char * name; int nargs; } KERNELS[GK_COUNT] = {
+        { "none", 0 }, { "binary_kernel", 2 }, { "unary_kernel", 2 }, { "rms_norm_kernel", 1 }, { "rms_norm_vec_kernel", 3 }, { "norm_kernel", 0 },
+        { "soft_max_wave_kernel", 1 }, { "soft_max_kernel", 1 }, { "rope_kernel", 0 }, { "memcpy", 0 }, { "cpy_kernel", 2 }, { "cpy_transpose_kernel", 2 },
+        { "get_rows_kernel", 1 }, { "get_rows_q_kernel", 1 }, { "mul_mat_f16_kernel", 1 }, { "mul_mat_dot_block_kernel", 0 }, { "mul_mat_dot_kernel", 1 },
+        { "argsort_kernel", 0 }, { "sum_rows_kernel", 0 }, { "rope_store_kernel", 1 }, { "moe_router_kernel", 0 }, { "moe_router_logits_kernel", 1 },
+        { "moe_combine_kernel", 0 }, { "moe_combine_add_norm_kernel", 1 } };
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        Spec s;
+        if (!parse_spec(line, s)) { fprintf(stderr, "bad spec: %s\n", line.c_str()); return 1; }
+        auto T = [&](const char * n) { return s.get(n); };
+        bool sup;
+        GluePlan p;
+        if (s.entry.compare(0, 3, "op:") == 0) {
+            const int op = op_id(s.entry.substr(3));
+            if ((sup = sup_op(op, T("a"), T("b"), T("c"), T("d")))) p = glue_op_plan(op, T("a"), T("b"), T("c"), T("d"));
+        } else if (s.entry == "add_rms_norm") {
+            if ((sup = sup_add_rms_norm(T("a"), T("b"), T("w"), T("sum"), T("d")))) p = glue_add_rms_norm_plan(T("a"), T("b"), T("w"), T("sum"), T("d"));
+        } else if (s.entry == "rope_store") {
+            if ((sup = sup_rope_kv_store(T("q"), T("pos"), T("ff"), T("qd"), T("k"), T("kd"), T("v"), T("vd")))) p = glue_rope_kv_store_plan(T("q"), T("k"), T("v"), T("vd"));
+        } else if (s.entry == "router") {
+            if ((sup = sup_moe_router(T("logits"), T("ids"), T("weights"), s.n_used))) p = glue_moe_router_plan(T("logits"));
+        } else if (s.entry == "router_logits") {
+            if ((sup = sup_moe_router_logits(T("gate"), T("x"), T("logits"), T("ids"), T("weights"), s.n_used))) p = glue_moe_router_logits_plan(T("x"), false);
+        } else if (s.entry == "router_logits_norm") {
+            if ((sup = sup_moe_router_logits_norm(T("gate"), T("x"), T("nw"), T("normed"), T("logits"), T("ids"), T("weights"), s.n_used))) p = glue_moe_router_logits_plan(T("x"), true);
+        } else if (s.entry == "combine") {
+            if ((sup = sup_moe_combine(T("x"), T("w"), T("out")))) p = glue_moe_combine_plan(T("x"), T("out"));
+        } else if (s.entry == "combine_add_rms_norm") {
+            if ((sup = sup_moe_combine_add_rms_norm(T("x"), T("w"), T("b"), T("nw"), T("sum"), T("d")))) p = glue_moe_combine_add_rms_norm_plan(T("x"));
+        } else { fprintf(stderr, "bad entry: %s\n", line.c_str()); return 1; }
+        if (!sup) { printf("unsupported\n"); continue; }
+        char label[96] = "none", kernel[96] = "none";
+        if (p.label) snprintf(label, sizeof(label), p.label, p.targ[0]);          // as QMM_TRACE formats it, while tracing
+        if (p.launch) {
+            int n = snprintf(kernel, sizeof(kernel), "%s", KERNELS[p.kernel].name);
+            for (int i = 0; i < KERNELS[p.kernel].nargs; ++i) n += snprintf(kernel + n, sizeof(kernel) - n, "%s%d", i ? "," : "<", p.targ[i]);
+            if (KERNELS[p.kernel].nargs) snprintf(kernel + n, sizeof(kernel) - n, ">");
+        }
+        printf("%s %s grid=%u,%u,%u block=%u lds=%zu karg=%u,%u ", label, kernel, p.grid[0], p.grid[1], p.grid[2], p.block, p.lds, p.karg[0], p.karg[1]);
+        if (p.err) printf("%d:%s\n", p.err, p.msg); else printf("ok\n");
+    }
+    return 0;
+}
+"""
+# (operands of one entry point, what the launch code did with them before the plan existed).  A spec: the entry point ("op:NAME" is qmm_op_compute),
+# then its operands by name as TYPE:extents[/byte strides][@address]; strides default to contiguous, addresses to 1 MiB slots; pi<i> / pf<i> set
+# op_params of the destination (rope: n_dims and mode, soft_max: scale and max_bias).  A result: trace label, instantiation (bools 0 / 1, element
+# types by their ids; none: nothing was launched or copied), grid, block, dynamic LDS bytes, the two grid-derived arguments of rope_store_kernel<1>,
+# then ok or the refusal's code and text; or "unsupported" where the entry point's support predicate turns the operands away.  The right-hand sides were printed by the launch code of the commit before this header (the support
+# predicates, the launch_* functions and every entry point of qmm_ops.hip) copied into a stand-alone program with each launch replaced by a
+# print, never by the header.  Every branch of every ladder on both sides of its boundary, one condition at a time.
+GLUE_PLAN_TABLE = [
+    ("op:ADD a=f32:4096,512 b=f32:4096 d=f32:4096,512",
+     "binary_kernel<vec> binary_kernel<1,1> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4098,3/4,16400,49200,49200 b=f32:4098/4,16400,16400,16400 d=f32:4098,3/4,16400,49200,49200",
+     "binary_kernel<scalar> binary_kernel<1,0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4100,3/4,16400,49200,49200 b=f32:4100/4,16400,16400,16400 d=f32:4100,3/4,16400,49200,49200",
+     "binary_kernel<vec> binary_kernel<1,1> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4096,512 b=f32:1,512/4,16,8192,8192 d=f32:4096,512",
+     "binary_kernel<scalar> binary_kernel<1,0> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4096,512 b=f32:4096/8,32768,32768,32768 d=f32:4096,512",
+     "binary_kernel<scalar> binary_kernel<1,0> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4096,512@0x100004 b=f32:4096 d=f32:4096,512",
+     "binary_kernel<scalar> binary_kernel<1,0> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4096,512 b=f32:4096@0x200004 d=f32:4096,512",
+     "binary_kernel<scalar> binary_kernel<1,0> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4096,512 b=f32:4096 d=f32:4096,512@0x300004",
+     "binary_kernel<scalar> binary_kernel<1,0> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4096,512/4,16388,8390656,8390656 b=f32:4096 d=f32:4096,512",
+     "binary_kernel<scalar> binary_kernel<1,0> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4096,512 b=f32:4096,512/4,16388,8390656,8390656 d=f32:4096,512",
+     "binary_kernel<scalar> binary_kernel<1,0> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ADD a=f32:4096,512 b=f32:4096 d=f32:4096,512/4,16388,8390656,8390656",
+     "binary_kernel<scalar> binary_kernel<1,0> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:1020,7 b=f32:1020,7 d=f32:1020,7",
+     "binary_kernel<vec> binary_kernel<3,1> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:1024,7 b=f32:1024,7 d=f32:1024,7",
+     "binary_kernel<vec> binary_kernel<3,1> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:1028,7 b=f32:1028,7 d=f32:1028,7",
+     "binary_kernel<vec> binary_kernel<3,1> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:255,7@0x100004 b=f32:255,7 d=f32:255,7",
+     "binary_kernel<scalar> binary_kernel<3,0> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:256,7@0x100004 b=f32:256,7 d=f32:256,7",
+     "binary_kernel<scalar> binary_kernel<3,0> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:257,7@0x100004 b=f32:257,7 d=f32:257,7",
+     "binary_kernel<scalar> binary_kernel<3,0> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:512,7 b=f32:512 d=f32:512,7",
+     "binary_kernel<vec> binary_kernel<3,1> grid=4,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:516,7 b=f32:516 d=f32:516,7",
+     "binary_kernel<vec> binary_kernel<3,1> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:128,7@0x100004 b=f32:128 d=f32:128,7",
+     "binary_kernel<scalar> binary_kernel<3,0> grid=4,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL a=f32:129,7 b=f32:129 d=f32:129,7",
+     "binary_kernel<scalar> binary_kernel<3,0> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SUB a=f32:64,35 b=f32:64 d=f32:64,35",
+     "binary_kernel<vec> binary_kernel<2,1> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:DIV a=f32:5,103 b=f32:5,103 d=f32:5,103",
+     "binary_kernel<scalar> binary_kernel<4,0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SUB a=f32:5,103 b=f32:1 d=f32:5,103",
+     "binary_kernel<scalar> binary_kernel<2,0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:DIV a=f32:64,5,7 b=f32:64,1,7 d=f32:64,5,7",
+     "binary_kernel<vec> binary_kernel<4,1> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SILU a=f32:0 d=f32:0",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 ok"),
+    ("op:SILU a=f32:1 d=f32:1",
+     "unary_kernel unary_kernel<6,0> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SILU a=f32:1024 d=f32:1024",
+     "unary_kernel unary_kernel<6,0> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SILU a=f32:1025 d=f32:1025",
+     "unary_kernel unary_kernel<6,0> grid=2,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SCALE a=f32:4096,3 d=f32:4096,3",
+     "unary_kernel unary_kernel<5,0> grid=12,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:EXP a=f32:4096,3 d=f32:4096,3",
+     "unary_kernel unary_kernel<13,0> grid=12,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SILU_MUL a=f32:4100,3 b=f32:4100,3 d=f32:4100,3",
+     "unary_kernel unary_kernel<6,1> grid=13,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SILU_MUL a=f32:0 b=f32:0 d=f32:0",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:4096,256 d=f32:4096,256",
+     "rms_norm_vec_kernel<256> rms_norm_vec_kernel<0,0,256> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:4096,256 b=f32:4096 d=f32:4096,256",
+     "rms_norm_vec_kernel<256> rms_norm_vec_kernel<1,0,256> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:4100,256 d=f32:4100,256",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<0,0,1024> grid=256,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:4100,256 b=f32:4100 d=f32:4100,256",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<1,0,1024> grid=256,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:4096,255 d=f32:4096,255",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<0,0,1024> grid=255,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:4096,255 b=f32:4096 d=f32:4096,255",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<1,0,1024> grid=255,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:16384,3 d=f32:16384,3",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<0,0,1024> grid=3,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:16384,3 b=f32:16384 d=f32:16384,3",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<1,0,1024> grid=3,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:16388,3 d=f32:16388,3",
+     "rms_norm_kernel rms_norm_kernel<0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:16388,3 b=f32:16388 d=f32:16388,3",
+     "rms_norm_kernel rms_norm_kernel<1> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:4098,3 d=f32:4098,3",
+     "rms_norm_kernel rms_norm_kernel<0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:4098,3 b=f32:4098 d=f32:4098,3",
+     "rms_norm_kernel rms_norm_kernel<1> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:16384,256 d=f32:16384,256",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<0,0,1024> grid=256,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:16384,256 b=f32:16384 d=f32:16384,256",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<1,0,1024> grid=256,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:4096,3@0x100004 d=f32:4096,3",
+     "rms_norm_kernel rms_norm_kernel<0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:4096,3 d=f32:4096,3@0x200004",
+     "rms_norm_kernel rms_norm_kernel<0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:4096,3 b=f32:4096@0x200004 d=f32:4096,3",
+     "rms_norm_kernel rms_norm_kernel<1> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:4096,3/4,16388,49164,49164 d=f32:4096,3",
+     "rms_norm_kernel rms_norm_kernel<0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:4098,3/4,16400,49200,49200 d=f32:4098,3/4,16400,49200,49200",
+     "rms_norm_kernel rms_norm_kernel<0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:4098,3/4,16400,49200,49200 b=f32:4098 d=f32:4098,3/4,16400,49200,49200",
+     "rms_norm_kernel rms_norm_kernel<1> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM a=f32:4100,3/4,16400,49200,49200 d=f32:4100,3/4,16400,49200,49200",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<0,0,1024> grid=3,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("op:RMS_NORM_MUL a=f32:4096,300 b=f32:4096 d=f32:4096,300/4,16388,4916400,4916400",
+     "rms_norm_kernel rms_norm_kernel<1> grid=300,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("add_rms_norm a=f32:4096,1 b=f32:4096,1 w=f32:4096 sum=f32:4096,1 d=f32:4096,1",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<1,1,1024> grid=1,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("add_rms_norm a=f32:4096,255 b=f32:4096,255 w=f32:4096 sum=f32:4096,255 d=f32:4096,255",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<1,1,1024> grid=255,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("add_rms_norm a=f32:4096,256 b=f32:4096,256 w=f32:4096 sum=f32:4096,256 d=f32:4096,256",
+     "rms_norm_vec_kernel<256> rms_norm_vec_kernel<1,1,256> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("add_rms_norm a=f32:4100,256 b=f32:4100,256 w=f32:4100 sum=f32:4100,256 d=f32:4100,256",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<1,1,1024> grid=256,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("add_rms_norm a=f32:16384,2 b=f32:16384,2 w=f32:16384 sum=f32:16384,2 d=f32:16384,2",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<1,1,1024> grid=2,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("add_rms_norm a=f32:4096,256 b=f32:4096,256 sum=f32:4096,256 d=f32:4096,256",
+     "rms_norm_vec_kernel<256> rms_norm_vec_kernel<0,1,256> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("add_rms_norm a=f32:4096,2 b=f32:4096,2 w=f32:4096 sum=f32:4096,2@0x400004 d=f32:4096,2",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 -5:ADD + RMS_NORM: rows must be 16-byte aligned, ne0 % 4 == 0 and ne0 <= 16384"),
+    ("add_rms_norm a=f32:4096,2 b=f32:4096,2@0x200004 w=f32:4096 sum=f32:4096,2 d=f32:4096,2",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 -5:ADD + RMS_NORM: rows must be 16-byte aligned, ne0 % 4 == 0 and ne0 <= 16384"),
+    ("add_rms_norm a=f32:4096,2@0x100004 b=f32:4096,2 sum=f32:4096,2 d=f32:4096,2",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 -5:ADD + RMS_NORM: rows must be 16-byte aligned, ne0 % 4 == 0 and ne0 <= 16384"),
+    ("add_rms_norm a=f32:4096,2 b=f32:4096,2 w=f32:4096@0x300004 sum=f32:4096,2 d=f32:4096,2",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 -5:ADD + RMS_NORM: rows must be 16-byte aligned, ne0 % 4 == 0 and ne0 <= 16384"),
+    ("add_rms_norm a=f32:4096,2 b=f32:4096,2 w=f32:4096 sum=f32:4096,2 d=f32:4096,2@0x500004",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 -5:ADD + RMS_NORM: rows must be 16-byte aligned, ne0 % 4 == 0 and ne0 <= 16384"),
+    ("add_rms_norm a=f32:4100,3/4,16400,49200,49200 b=f32:4100,3/4,16400,49200,49200 w=f32:4100 sum=f32:4100,3/4,16400,49200,49200 d=f32:4100,3/4,16400,49200,49200",
+     "rms_norm_vec_kernel<1024> rms_norm_vec_kernel<1,1,1024> grid=3,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("add_rms_norm a=f32:4098,3/4,16400,49200,49200 b=f32:4098,3/4,16400,49200,49200 w=f32:4098 sum=f32:4098,3/4,16400,49200,49200 d=f32:4098,3/4,16400,49200,49200",
+     "unsupported"),
+    ("add_rms_norm a=f32:16388,3 b=f32:16388,3 w=f32:16388 sum=f32:16388,3 d=f32:16388,3",
+     "unsupported"),
+    ("op:NORM a=f32:100,7,3 d=f32:100,7,3",
+     "norm_kernel norm_kernel grid=21,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ROPE a=f32:66,3,5 b=i32:5 d=f32:66,3,5 pi1=64 pi2=2",
+     "rope_kernel rope_kernel grid=2,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ROPE a=f32:128,32,4 b=i32:4 c=f32:64 d=f32:128,32,4 pi1=128 pi2=0",
+     "rope_kernel rope_kernel grid=32,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:ARGSORT a=f32:100,7 d=i32:100,7 pi0=1",
+     "argsort_kernel argsort_kernel grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SUM_ROWS a=f32:100,7 d=f32:1,7",
+     "sum_rows_kernel sum_rows_kernel grid=2,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SUM_ROWS a=f32:100,8 d=f32:1,8",
+     "sum_rows_kernel sum_rows_kernel grid=2,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:256,32,32 b=f32:256,32 d=f32:256,32,32",
+     "soft_max_wave_kernel<1> soft_max_wave_kernel<1> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:260,32,32 b=f32:260,32 d=f32:260,32,32",
+     "soft_max_wave_kernel<2> soft_max_wave_kernel<2> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:512,32,32 b=f32:512,32 d=f32:512,32,32",
+     "soft_max_wave_kernel<2> soft_max_wave_kernel<2> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:516,32,32 b=f32:516,32 d=f32:516,32,32",
+     "soft_max_wave_kernel<4> soft_max_wave_kernel<4> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:1024,32,32 b=f32:1024,32 d=f32:1024,32,32",
+     "soft_max_wave_kernel<4> soft_max_wave_kernel<4> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:1028,32,32 b=f32:1028,32 d=f32:1028,32,32",
+     "soft_max_kernel<lds> soft_max_kernel<0> grid=1024,1,1 block=256 lds=4112 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:256,1023 d=f32:256,1023",
+     "soft_max_kernel<lds> soft_max_kernel<0> grid=1023,1,1 block=256 lds=1024 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:256,1024 d=f32:256,1024",
+     "soft_max_wave_kernel<1> soft_max_wave_kernel<1> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:256,1025 d=f32:256,1025",
+     "soft_max_wave_kernel<1> soft_max_wave_kernel<1> grid=257,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:254,32,32 b=f32:254,32 d=f32:254,32,32",
+     "soft_max_kernel<lds> soft_max_kernel<0> grid=1024,1,1 block=256 lds=1016 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:256,32,32 b=f32:256,32 d=f32:256,32,32 pf0=0.125 pf1=8",
+     "soft_max_kernel<lds> soft_max_kernel<0> grid=1024,1,1 block=256 lds=1024 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:256,32,32 b=f16:256,32 d=f32:256,32,32",
+     "soft_max_kernel<lds> soft_max_kernel<1> grid=1024,1,1 block=256 lds=1024 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:256,32,32 b=f32:256,32@0x200004 d=f32:256,32,32",
+     "soft_max_kernel<lds> soft_max_kernel<0> grid=1024,1,1 block=256 lds=1024 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:256,32,32@0x100004 b=f32:256,32 d=f32:256,32,32",
+     "soft_max_kernel<lds> soft_max_kernel<0> grid=1024,1,1 block=256 lds=1024 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:256,32,32 b=f32:256,32 d=f32:256,32,32@0x300004",
+     "soft_max_kernel<lds> soft_max_kernel<0> grid=1024,1,1 block=256 lds=1024 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:8192,3 b=f16:8192,3 d=f32:8192,3",
+     "soft_max_kernel<lds> soft_max_kernel<1> grid=3,1,1 block=256 lds=32768 karg=0,0 ok"),
+    ("op:SOFT_MAX a=f32:8196,3 b=f32:8196,4 d=f32:8196,3",
+     "soft_max_kernel<dst> soft_max_kernel<0> grid=3,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:64,64 d=f32:64,64",
+     "memcpy memcpy grid=0,0,0 block=0 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f16:64,64@0x100000 d=f16:64,64@0x100000",
+     "memcpy none grid=0,0,0 block=0 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:64,64@0x100000 d=f32:4096@0x100000",
+     "memcpy none grid=0,0,0 block=0 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:64,64/4,512,32768,32768 d=f32:64,64",
+     "cpy_kernel cpy_kernel<0,0> grid=16,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f16:10,10,10 d=f32:1000",
+     "cpy_kernel cpy_kernel<1,0> grid=4,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:0 d=f16:0",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:32,8/32,4,1024,1024 d=f32:32,8",
+     "cpy_transpose_kernel cpy_transpose_kernel<0,0> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:32,8/32,4,1024,1024 d=f16:32,8",
+     "cpy_transpose_kernel cpy_transpose_kernel<0,1> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f16:32,8/16,2,512,512 d=f32:32,8",
+     "cpy_transpose_kernel cpy_transpose_kernel<1,0> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f16:32,8/16,2,512,512 d=f16:32,8",
+     "cpy_transpose_kernel cpy_transpose_kernel<1,1> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:31,8/32,4,992,992 d=f32:31,8",
+     "cpy_kernel cpy_kernel<0,0> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:31,8/32,4,992,992 d=f16:31,8",
+     "cpy_kernel cpy_kernel<0,1> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f16:31,8/16,2,496,496 d=f32:31,8",
+     "cpy_kernel cpy_kernel<1,0> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f16:31,8/16,2,496,496 d=f16:31,8",
+     "cpy_kernel cpy_kernel<1,1> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:32,7/28,4,896,896 d=f32:32,7",
+     "cpy_kernel cpy_kernel<0,0> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f16:32,7/14,2,448,448 d=f32:32,7",
+     "cpy_kernel cpy_kernel<1,0> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f16:32,7/14,2,448,448 d=f16:32,7",
+     "cpy_kernel cpy_kernel<1,1> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:32,8/32,4,1024,1024 d=f16:32,8/4,128,1024,1024",
+     "cpy_kernel cpy_kernel<0,1> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:32,7/28,4,896,896 d=f16:32,7",
+     "cpy_kernel cpy_kernel<0,1> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:1024,70/280,4,286720,286720 d=f16:1024,70/2,4096,286720,286720",
+     "cpy_transpose_kernel cpy_transpose_kernel<0,1> grid=32,3,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:32,8,2/32,4,1024,2048 d=f16:32,8,2",
+     "cpy_kernel cpy_kernel<0,1> grid=2,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:CPY a=f32:32,8/64,8,2048,2048 d=f16:32,8",
+     "cpy_kernel cpy_kernel<0,1> grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:GET_ROWS a=f32:64,100 b=i32:7 d=f32:64,7",
+     "get_rows_kernel get_rows_kernel<0> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:GET_ROWS a=f16:64,100,2 b=i32:7,2 d=f32:64,7,2",
+     "get_rows_kernel get_rows_kernel<1> grid=14,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:GET_ROWS a=t12:4096,100 b=i32:7 d=f32:4096,7",
+     "get_rows_q_kernel<12> get_rows_q_kernel<12> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:GET_ROWS a=t8:4096,100 b=i32:300 d=f32:4096,300",
+     "get_rows_q_kernel<8> get_rows_q_kernel<8> grid=300,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f16:64,70,2 b=f32:64,65,4 d=f32:70,65,4",
+     "mul_mat_f16_kernel<vec> mul_mat_f16_kernel<1> grid=2,2,4 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f16:64,70,2@0x100004 b=f32:64,65,4 d=f32:70,65,4",
+     "mul_mat_f16_kernel<scalar> mul_mat_f16_kernel<0> grid=2,2,4 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f16:64,70,2/2,136,9520,19040 b=f32:64,65,4 d=f32:70,65,4",
+     "mul_mat_f16_kernel<scalar> mul_mat_f16_kernel<0> grid=2,2,4 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f16:64,70,2 b=f32:64,65,4@0x200004 d=f32:70,65,4",
+     "mul_mat_f16_kernel<scalar> mul_mat_f16_kernel<0> grid=2,2,4 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f16:64,70,2 b=f32:64,65,4/4,260,16900,67600 d=f32:70,65,4",
+     "mul_mat_f16_kernel<scalar> mul_mat_f16_kernel<0> grid=2,2,4 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f16:64,70,2 b=f32:64,65,4 d=f32:70,65,4@0x300004",
+     "mul_mat_f16_kernel<vec> mul_mat_f16_kernel<1> grid=2,2,4 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f16:128,640,8/2,2048,256,1310720 b=f32:128,512,32/4,16384,512,8388608 d=f32:640,512,32",
+     "mul_mat_f16_kernel<vec> mul_mat_f16_kernel<1> grid=10,8,32 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f32:1024,2048 b=f32:1024,1 d=f32:2048,1",
+     "mul_mat_dot_block_kernel mul_mat_dot_block_kernel grid=2048,1,1 block=128 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f32:1024,2049 b=f32:1024,1 d=f32:2049,1",
+     "mul_mat_dot_kernel mul_mat_dot_kernel<0> grid=513,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f32:1023,2048 b=f32:1023,1 d=f32:2048,1",
+     "mul_mat_dot_kernel mul_mat_dot_kernel<0> grid=512,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f32:1024,8 b=f32:1024,3,2,2 d=f32:8,3,2,2",
+     "mul_mat_dot_block_kernel mul_mat_dot_block_kernel grid=24,1,4 block=128 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f32:4096,8 b=f32:4096,1 d=f32:8,1",
+     "mul_mat_dot_block_kernel mul_mat_dot_block_kernel grid=8,1,1 block=128 lds=0 karg=0,0 ok"),
+    ("op:MUL_MAT_F a=f32:64,9,2 b=f32:64,5,4 d=f32:9,5,4",
+     "mul_mat_dot_kernel mul_mat_dot_kernel<0> grid=12,1,4 block=256 lds=0 karg=0,0 ok"),
+    ("rope_store q=f32:128,32,4 pos=i32:4 qd=f32:128,32,4 pi1=128 pi2=0 k=f32:128,8,4 kd=f16:128,8,4 v=f32:32,32/128,4,4096,4096 vd=f16:32,32",
+     "none rope_store_kernel<1> grid=6,1,1 block=256 lds=0 karg=5,1 ok"),
+    ("rope_store q=f32:128,32,4 pos=i32:4 qd=f32:128,32,4 pi1=128 pi2=0 k=f32:128,8,4 kd=f16:128,8,4 v=f32:31,32/128,4,3968,3968 vd=f16:31,32",
+     "none rope_store_kernel<0> grid=9,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("rope_store q=f32:128,32,4 pos=i32:4 qd=f32:128,32,4 pi1=128 pi2=0 k=f32:128,8,4 kd=f16:128,8,4 v=f32:32,31/124,4,3968,3968 vd=f16:32,31",
+     "none rope_store_kernel<0> grid=9,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("rope_store q=f32:128,32,4 pos=i32:4 qd=f32:128,32,4 pi1=128 pi2=0 k=f32:128,8,4 kd=f16:128,8,4 v=f32:1024,70/280,4,286720,286720 vd=f16:1024,70",
+     "none rope_store_kernel<1> grid=101,1,1 block=256 lds=0 karg=5,32 ok"),
+    ("rope_store q=f32:128,32,4 pos=i32:4 qd=f32:128,32,4 pi1=128 pi2=0 v=f32:32,32/128,4,4096,4096 vd=f16:32,32",
+     "none rope_store_kernel<1> grid=5,1,1 block=256 lds=0 karg=4,1 ok"),
+    ("rope_store q=f32:128,32,4 pos=i32:4 qd=f32:128,32,4 pi1=128 pi2=0 k=f32:128,8,4 kd=f16:128,8,4",
+     "none rope_store_kernel<0> grid=5,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("rope_store q=f32:128,32,4 pos=i32:4 qd=f32:128,32,4 pi1=128 pi2=0",
+     "none rope_store_kernel<0> grid=4,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("rope_store q=f32:128,12,3 pos=i32:3 ff=f32:32 qd=f32:128,12,3 pi1=64 pi2=2 k=f32:128,3,3 kd=f16:128,3,3 v=f32:384,3 vd=f16:3,384",
+     "none rope_store_kernel<0> grid=7,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("rope_store q=f32:128,32,4 pos=i32:4 qd=f32:128,32,4 pi1=128 pi2=0 k=f32:128,8,4 kd=f16:128,8,4 v=f32:1024,4 vd=f16:4,1024/2,8192,8388608,8388608",
+     "none rope_store_kernel<0> grid=21,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("router logits=f32:8,1 ids=i32:8,1 weights=f32:2,1 n_used=2",
+     "none moe_router_kernel grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("router logits=f32:8,4 ids=i32:8,4 weights=f32:2,4 n_used=2",
+     "none moe_router_kernel grid=1,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("router logits=f32:8,5 ids=i32:8,5 weights=f32:2,5 n_used=2",
+     "none moe_router_kernel grid=2,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("router logits=f32:64,512 ids=i32:64,512 weights=f32:6,512 n_used=6",
+     "none moe_router_kernel grid=128,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("router_logits gate=f32:4096,8 x=f32:4096,1 logits=f32:8,1 ids=i32:8,1 weights=f32:2,1 n_used=2",
+     "none moe_router_logits_kernel<0> grid=1,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("router_logits gate=f32:1024,8 x=f32:1024,8 logits=f32:8,8 ids=i32:8,8 weights=f32:2,8 n_used=2",
+     "none moe_router_logits_kernel<0> grid=8,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("router_logits_norm gate=f32:4096,8 x=f32:4096,1 nw=f32:4096 normed=f32:4096,1 logits=f32:8,1 ids=i32:8,1 weights=f32:2,1 n_used=2",
+     "none moe_router_logits_kernel<1> grid=1,1,1 block=1024 lds=16384 karg=0,0 ok"),
+    ("router_logits_norm gate=f32:16384,8 x=f32:16384,8 nw=f32:16384 normed=f32:16384,8 logits=f32:8,8 ids=i32:8,8 weights=f32:2,8 n_used=2",
+     "none moe_router_logits_kernel<1> grid=8,1,1 block=1024 lds=65536 karg=0,0 ok"),
+    ("router_logits_norm gate=f32:4098,8/4,16400,131200,131200 x=f32:4098,1/4,16400,16400,16400 nw=f32:4098 normed=f32:4098,1/4,16400,16400,16400 logits=f32:8,1 ids=i32:8,1 weights=f32:2,1 n_used=2",
+     "unsupported"),
+    ("router_logits_norm gate=f32:4100,8 x=f32:4100,1 nw=f32:4100 normed=f32:4100,1 logits=f32:8,1 ids=i32:8,1 weights=f32:2,1 n_used=2",
+     "none moe_router_logits_kernel<1> grid=1,1,1 block=1024 lds=16400 karg=0,0 ok"),
+    ("combine x=f32:1024,2,3 w=f32:1,2,3 out=f32:1024,3",
+     "none moe_combine_kernel grid=1,3,1 block=256 lds=0 karg=0,0 ok"),
+    ("combine x=f32:1028,2,3 w=f32:1,2,3 out=f32:1028,3",
+     "none moe_combine_kernel grid=2,3,1 block=256 lds=0 karg=0,0 ok"),
+    ("combine x=f32:4096,2,1@0x100004 w=f32:1,2,1 out=f32:4096,1",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 -1:qmm_moe_combine: x / out must be 16-byte aligned"),
+    ("combine x=f32:4096,2,1 w=f32:1,2,1 out=f32:4096,1@0x300004",
+     "none none grid=0,0,0 block=0 lds=0 karg=0,0 -1:qmm_moe_combine: x / out must be 16-byte aligned"),
+    ("combine_add_rms_norm x=f32:4096,2,1 w=f32:1,2,1 b=f32:4096,1 nw=f32:4096 sum=f32:4096,1 d=f32:4096,1",
+     "none moe_combine_add_norm_kernel<1024> grid=1,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("combine_add_rms_norm x=f32:4096,2,255 w=f32:1,2,255 b=f32:4096,255 nw=f32:4096 sum=f32:4096,255 d=f32:4096,255",
+     "none moe_combine_add_norm_kernel<1024> grid=255,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("combine_add_rms_norm x=f32:4096,2,256 w=f32:1,2,256 b=f32:4096,256 nw=f32:4096 sum=f32:4096,256 d=f32:4096,256",
+     "none moe_combine_add_norm_kernel<256> grid=256,1,1 block=256 lds=0 karg=0,0 ok"),
+    ("combine_add_rms_norm x=f32:4100,2,256 w=f32:1,2,256 b=f32:4100,256 nw=f32:4100 sum=f32:4100,256 d=f32:4100,256",
+     "none moe_combine_add_norm_kernel<1024> grid=256,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("combine_add_rms_norm x=f32:16384,2,256 w=f32:1,2,256 b=f32:16384,256 nw=f32:16384 sum=f32:16384,256 d=f32:16384,256",
+     "none moe_combine_add_norm_kernel<1024> grid=256,1,1 block=1024 lds=0 karg=0,0 ok"),
+    ("combine_add_rms_norm x=f32:16388,2,2 w=f32:1,2,2 b=f32:16388,2 nw=f32:16388 sum=f32:16388,2 d=f32:16388,2",
+     "unsupported"),
+]
+
+
+@pytest.fixture(scope="module")
+def glue_plan_probe(tmp_path_factory):
+    """the plan header alone, compiled by the host compiler (no HIP, no ggml) into a program that prints the plan of each operand spec on its input"""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    d = tmp_path_factory.mktemp("glueplan")
+    (d / "probe.cpp").write_text(GLUE_PLAN_PROBE)
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", f"-I{GLUE_PLAN_HEADER.parent}", str(d / "probe.cpp"), "-o", str(d / "probe")], check=True)
+    return lambda specs: subprocess.run([str(d / "probe")], input="\n".join(specs) + "\n", check=True, capture_output=True, text=True).stdout.splitlines()
+
+
+def test_glue_plan_keeps_every_decision(glue_plan_probe):
+    assert len(GLUE_PLAN_TABLE) >= 80
+    got = glue_plan_probe([spec for spec, _ in GLUE_PLAN_TABLE])
+    assert len(got) == len(GLUE_PLAN_TABLE)
+    for (spec, want), line in zip(GLUE_PLAN_TABLE, got):
+        assert line == want, spec
+
+
+def test_glue_rules_live_in_one_place():
+    """the plan functions, the support predicates and the rules two kernels share are defined in the plan header only; a glue kernel is launched
+    only by run_glue of qmm_ops.hip; one QMM_TRACE serves the glue launches, in run_glue (comments may speak of all this)"""
+    def code_of(f):
+        return [re.sub(r"//.*$", "", line) for line in f.read_text().splitlines()]
+    defines = re.compile(r"\b(?:GluePlan|bool|int)\s+(glue_\w*plan|sup_\w+|row_norm_\w+|transpose_2d)\s*\(")
+    found = sorted(m.group(1) for line in code_of(GLUE_PLAN_HEADER) for m in defines.finditer(line))
+    assert len(found) == len(set(found))
+    for name in ("glue_op_plan", "glue_add_rms_norm_plan", "glue_rope_kv_store_plan", "glue_moe_router_plan", "glue_moe_router_logits_plan", "glue_moe_combine_plan",
+                 "glue_moe_combine_add_rms_norm_plan", "sup_op", "sup_add_rms_norm", "sup_rope_kv_store", "sup_moe_router", "sup_moe_router_logits",
+                 "sup_moe_router_logits_norm", "sup_moe_combine", "sup_moe_combine_add_rms_norm", "row_norm_threads", "row_norm_in_regs", "transpose_2d"):
+        assert name in found, name
+    kernels = set()                                                          # every __global__ function of the unit that is not of the attention section
+    unit = code_of(GLUE_UNIT)
+    for n, line in enumerate(unit):
+        if "__global__" in line:
+            kernels.update(re.findall(r"^(\w+_kernel)\s*\(", unit[n + 1]))
+    assert len(kernels) >= 22, sorted(kernels)
+    launch = re.compile(r"hipLaunchKernelGGL\s*\((.*)$")
+    traces = 0
+    for f in sorted((ROOT / "ggml-hexagon_amd" / "csrc").iterdir()):
+        if f.suffix not in (".cpp", ".h", ".hip", ".hiph"):
+            continue
+        inside = None                                                        # the function a line belongs to: the last line that opened one at column 0
+        for n, line in enumerate(code_of(f), 1):
+            where = f"{f.name}:{n}: {line.strip()[:120]}"
+            if re.match(r"^\w.*\)\s*\{", line):
+                inside = line
+            if f != GLUE_PLAN_HEADER:
+                assert not defines.search(line), where
+                assert not re.search(r"rows\s*<\s*256|>\s*256\s*\*\s*16|<=\s*1024\s*\*\s*16", line), where          # the row-norm rules, spelled out
+            m = launch.search(line)
+            if m and (f == GLUE_UNIT or any(re.search(rf"\b{k}\b", m.group(1)) for k in kernels)):
+                assert f == GLUE_UNIT and inside is not None and re.search(r"\brun_glue\s*\(", inside), where
+            if f == GLUE_UNIT and "QMM_TRACE" in line:
+                traces += 1
+                assert inside is not None and re.search(r"\brun_glue\s*\(", inside), where
+    assert traces == 1
