@@ -3,12 +3,11 @@
 
 #include "qmm_host.h"
 
-#include <algorithm>
-
 #include "qmm_matvec.hiph"
-#include "qmm_mfma.hiph"
+#include "qmm_mfma.hiph"              // the prefill kernels ...
 #include "qmm_mfma_regb.hiph"
 #include "qmm_mfma_r64s.hiph"
+#include "qmm_prefill.hiph"           // ... and, behind them, what launches them
 #include "qmm_moe.hiph"
 #include "qmm_chain.hiph"
 
@@ -256,7 +255,6 @@ qmm_ctx * qmm_create(int device) {
     c->prep_reg       = sw[qmm_sw::SW_PREP_REG];
     c->regb_q23       = sw[qmm_sw::SW_REGB_Q23] != 0;
     c->mv_onepass     = sw[qmm_sw::SW_MV_ONEPASS];
-    c->side_on        = sw[qmm_sw::SW_SIDE];
     c->splitk_combine = sw[qmm_sw::SW_SPLITK_COMBINE];
     c->chain_enabled  = sw.is_set(qmm_sw::SW_CHAIN) ? sw[qmm_sw::SW_CHAIN] : 1;      // (the table's default is the plugin's: no chains unless asked)
     c->mv_bpc         = sw[qmm_sw::SW_MV_BPC];
@@ -278,11 +276,6 @@ void qmm_destroy(qmm_ctx * c) {
     if (c->chain_sync) (void) hipFree(c->chain_sync);
     delete c->chain;
     delete c->trace;
-    for (int l = 0; l < 3; ++l) {
-        if (c->side[l]) (void) hipStreamDestroy(c->side[l]);
-        if (c->ev_join[l]) (void) hipEventDestroy(c->ev_join[l]);
-    }
-    if (c->ev_fork) (void) hipEventDestroy(c->ev_fork);
     if (c->stream) (void) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -561,8 +554,9 @@ int qmm_quantize_act(qmm_ctx * c, int vt, const float * x, int64_t rows, int64_t
 
 // ------------------------------------------------------------------------------------------- mat-vec
 
+// `ex`: what the few-token kernels fold in (N <= QMM_MATVEC_MAX_N); `in`: what the activation prep of a prompt batch forms (above)
 static int mul_mat_group_impl(qmm_ctx * c, const qmm_weight * ws, int nw, int64_t K, const float * x, int64_t N, int64_t ldx, void * stream,
-                              const qmm_mv_extra * ex) {
+                              const qmm_mv_extra * ex, const PrefillInput & in = PrefillInput{}) {
     if (!c || !ws || nw <= 0) return fail(QMM_EINVAL, "qmm_mul_mat_group: bad arguments");
     if (N <= 0) return QMM_OK;
     if (ex) {                                                    // few-token extras: validated by the plan header, whatever N
@@ -599,71 +593,10 @@ static int mul_mat_group_impl(qmm_ctx * c, const qmm_weight * ws, int nw, int64_
         }
         return QMM_OK;
     }
+    // a prompt batch: the group shares src1, whose 16-bit operand is prepared once per activation format (key); the group's plan
+    // (qmm_prefill_plan.h) lists the launches, run_prefill_group (qmm_prefill.hiph) issues them
     c->mfma_calls++;
-    // The group shares src1: its 16-bit operand is prepared once per activation format (key).  Runs of same-type matrices are one tiled
-    // launch each where the shapes allow (the run's plan, qmm_prefill_plan.h).  A run with a NEW key has nothing in common with what was issued before
-    // it except src1: it goes to a side stream (own workspace slice) between a fork and a join event, so that its prep / MFMA / reduce
-    // launches overlap the earlier runs' instead of queueing behind them; a run that reuses a prep stays on that prep's stream.
-    struct Run { int i, j, lane; PrefillPlan plan; };
-    Run runs[MV_MAX_GROUP * 2];
-    int nruns = 0;
-    const PrefillRules rules = prefill_rules(c);
-    for (int i = 0; i < nw;) {
-        if (ws[i].M == 0) { ++i; continue; }
-        int64_t M[4] = { ws[i].M };
-        const int key = prefill_prep_key(rules, ws[i].type, ws[i].M, K, N);
-        int j = i + 1;
-        while (j < nw && j - i < 4 && ws[j].type == ws[i].type && ws[j].M > 0) { M[j - i] = ws[j].M; ++j; }
-        for (int k = i + 1; k < j; ++k) if (prefill_prep_key(rules, ws[k].type, ws[k].M, K, N) != key) j = i + 1;
-        if (nruns == (int) (sizeof(runs) / sizeof(runs[0]))) return fail(QMM_EUNSUPPORTED, "qmm_mul_mat_group: too many runs in one group");
-        runs[nruns++] = { i, j, 0, prefill_plan(rules, ws[i].type, M, j - i, K, N, 1, prefill_flags(c)) };
-        i = j;
-    }
-    int nlanes = 1;                                              // lane 0 = the caller's stream, 1..3 = side streams
-    const bool side = c->side_on && nruns > 1 && !c->prep_x2;
-    for (int r = 1; r < nruns; ++r) {
-        int found = -1;
-        for (int q = 0; q < r; ++q) if (runs[q].plan.key == runs[r].plan.key) found = runs[q].lane;      // reuses that run's prep: same stream, behind it
-        runs[r].lane = found >= 0 ? found : (side && nlanes < 4 ? nlanes++ : 0);
-    }
-    // disjoint workspace slices, each as large as the largest plan of its lane's runs (they follow each other on the lane's stream and share
-    // the operand); all of it allocated before the first launch, so that no run moves the workspace under a prepared operand
-    size_t lane_base[4] = { 0, 0, 0, 0 };
-    {
-        size_t lane_bytes[4] = { 0, 0, 0, 0 }, base = 0;
-        for (int r = 0; r < nruns; ++r) lane_bytes[runs[r].lane] = std::max(lane_bytes[runs[r].lane], runs[r].plan.ws_total);
-        for (int l = 0; l < nlanes; ++l) { lane_base[l] = base; base += (lane_bytes[l] + 255) & ~(size_t) 255; }
-        const int rc = ensure_ws(c, base);
-        if (rc) return rc;
-    }
-    if (nlanes > 1) {
-        for (int l = 1; l < nlanes; ++l) {
-            if (!c->side[l - 1]) HIP_TRY(hipStreamCreateWithFlags(&c->side[l - 1], hipStreamNonBlocking));
-            if (!c->ev_join[l - 1]) HIP_TRY(hipEventCreateWithFlags(&c->ev_join[l - 1], hipEventDisableTiming));
-        }
-        if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->ev_fork, st));
-        for (int l = 1; l < nlanes; ++l) HIP_TRY(hipStreamWaitEvent(c->side[l - 1], c->ev_fork, 0));
-    }
-    int lane_key[4] = { -1, -1, -1, -1 };
-    int rc = QMM_OK;
-    // side lanes first: their (small) launches are in the queues when the caller's stream starts on the big run
-    for (int pass = 0; pass < 2 && rc == QMM_OK; ++pass)
-        for (int r = 0; r < nruns && rc == QMM_OK; ++r) {
-            const Run & R = runs[r];
-            if ((pass == 0) != (R.lane != 0)) continue;
-            c->ws_base = lane_base[R.lane];
-            hipStream_t ls = R.lane ? c->side[R.lane - 1] : st;
-            rc = mfma_mul_mat(c, ls, R.plan, ws[R.i].type, ws + R.i, R.j - R.i, K, x, N, ldx, R.plan.key == lane_key[R.lane]);
-            lane_key[R.lane] = R.plan.key;
-        }
-    c->ws_base = 0;
-    for (int l = 1; l < nlanes; ++l) {                           // join on every path: a capture must not end with a dangling side stream
-        const hipError_t e1 = hipEventRecord(c->ev_join[l - 1], c->side[l - 1]);
-        const hipError_t e2 = hipStreamWaitEvent(st, c->ev_join[l - 1], 0);
-        if (rc == QMM_OK && (e1 != hipSuccess || e2 != hipSuccess)) rc = fail(QMM_EHIP, "qmm_mul_mat_group: joining the side stream failed");
-    }
-    return rc;
+    return run_prefill_group(c, st, ws, nw, K, x, N, ldx, in);
 }
 
 // dst = W * (silu(gate) .* up) for a prompt batch: ffn_down with the SwiGLU product formed by the activation prep of the MFMA path
@@ -676,12 +609,9 @@ int qmm_mul_mat_swiglu_in(qmm_ctx * c, int type, const void * w, int64_t w_row_b
     if (c->prec != QMM_PREC_F16_Q8) return fail(QMM_EUNSUPPORTED, "qmm_mul_mat_swiglu_in: only in the default prefill mode");
     if ((uintptr_t) up % 16 || ld_up % 4 || ld_up < K) return fail(QMM_EINVAL, "qmm_mul_mat_swiglu_in: up must be 16-byte aligned, ld_up %% 4 == 0, ld_up >= K");
     const qmm_weight ws = { w, w_row_bytes, M, dst, ldd, type };
-    c->prep_x2 = up;
-    c->prep_ldx2 = ld_up;
-    const int rc = mul_mat_group_impl(c, &ws, 1, K, gate, N, ld_gate, stream, nullptr);
-    c->prep_x2 = nullptr;
-    c->prep_ldx2 = 0;
-    return rc;
+    PrefillInput in;
+    in.x2 = up;  in.ldx2 = ld_up;
+    return mul_mat_group_impl(c, &ws, 1, K, gate, N, ld_gate, stream, nullptr, in);
 }
 
 int qmm_mul_mat_group(qmm_ctx * c, const qmm_weight * ws, int nw, int64_t K, const float * x, int64_t N, int64_t ldx, void * stream) {
@@ -708,13 +638,9 @@ int qmm_mul_mat_group_ex(qmm_ctx * c, const qmm_weight * ws, int nw, int64_t K, 
         if (ex->norm_eps < 0.0f || (uintptr_t) ex->norm_w % 16 || (uintptr_t) x % 16 || ldx % 4 || (ex->norm_add && ((uintptr_t) ex->norm_add % 16 || ex->norm_add_ld % 4 || !ex->norm_sum)) ||
             (ex->norm_sum && ((uintptr_t) ex->norm_sum % 16 || ex->norm_sum_ld % 4)))
             return fail(QMM_EINVAL, "qmm_mul_mat_group_ex: norm operands must be 16-byte aligned rows, eps >= 0, a sum buffer with norm_add");
-        c->prep_norm = qmm_ctx::prep_norm_t{};
-        c->prep_norm.w = ex->norm_w;  c->prep_norm.eps = ex->norm_eps;
-        c->prep_norm.add = ex->norm_add;  c->prep_norm.ld_add = ex->norm_add_ld;
-        c->prep_norm.sum = ex->norm_add ? ex->norm_sum : nullptr;  c->prep_norm.ld_sum = ex->norm_sum_ld;
-        const int rc = mul_mat_group_impl(c, ws, nw, K, x, N, ldx, stream, nullptr);
-        c->prep_norm = qmm_ctx::prep_norm_t{};
-        return rc;
+        PrefillInput in;
+        in.norm = { ex->norm_w, ex->norm_eps, ex->norm_add, ex->norm_add_ld, ex->norm_add ? ex->norm_sum : nullptr, ex->norm_sum_ld };
+        return mul_mat_group_impl(c, ws, nw, K, x, N, ldx, stream, nullptr, in);
     }
     return mul_mat_group_impl(c, ws, nw, K, x, N, ldx, stream, ex);
 }

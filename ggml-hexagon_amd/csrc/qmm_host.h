@@ -28,28 +28,15 @@ struct qmm_ctx {
     int         skinny = 1;          // few-token split-K MFMA kernel (GGML_MI355X_SKINNY=0 turns it off)
     int         skinny_max_n = 64;   // ... used for 8 < N <= this, and up to skinny_max_n_few when the matrix has no more
     int         skinny_max_n_few = 128;  //     32-row groups than the chip has CUs (GGML_MI355X_SKINNY_MAXN sets both)
-    // workspace of the batched path (16-bit activations, row scales, MoE lists); grown on demand
+    // workspace of the batched path (16-bit activations, row scales, split-K slabs, MoE lists); grown on demand, sized once per call
     void *      ws = nullptr;
     size_t      ws_bytes = 0;
-    size_t      ws_base = 0, ws_used = 0;   // prefill runs that are in flight together use disjoint slices: a run works at ws + ws_base and reports what it took
-    // Runs of a prefill group that need their own activation prep (another weight format: attn_v in Q6_K beside attn_q / attn_k in
-    // Q4_K) go out on side streams between a fork and a join event: their prep / MFMA / reduce launches, each too small to fill the
-    // chip, overlap the first run's instead of queueing behind them (GGML_MI355X_SIDE=0: one stream)
-    int         side_on = 0;             // (measured on llama3-8b q/k/v with attn_v in Q6_K: 74 us one stream, 78.5 us with the Q6_K run on a side stream: the two events cost more than the overlap wins)
-    hipStream_t side[3] = { nullptr, nullptr, nullptr };
-    hipEvent_t  ev_fork = nullptr, ev_join[3] = { nullptr, nullptr, nullptr };
     int         splitk_combine = 0;  // GGML_MI355X_SPLITK_COMBINE=1: split-K ranges combined inside the launch (splitk_finish_wave) instead of by splitk_reduce_kernel.
                                      // Bit-identical, measured a wash on llama3-8b at 512 tokens (wo 46.1 -> 43.9 us, q/k/v 72.4 -> 73.0, ffn_down 105.5 -> 107.1): the
                                      // slabs' traffic stays, and the last arriver's four dependent read trips cost what the reduce launch cost.  Opt-in.
     int *       kcnt = nullptr;      // its arrival counters (zero between launches), one per (row tile, token tile, wave)
     int64_t     kcnt_n = 0;
     int *       flag = nullptr;      // device word set by kernels that meet an expert id out of range
-    const float * prep_x2 = nullptr; // transient: second operand of a SwiGLU input while qmm_mul_mat_swiglu_in runs (prefill prep)
-    int64_t     prep_ldx2 = 0;
-    // transient: while qmm_mul_mat_group_ex runs a prefill group with extra->norm_w, the activation prep forms rms_norm(x [+ add]) * w itself
-    // (prep_act_q8k_kernel<..., NORM>); behind the first prep of the call x is the stored sum, read as it is
-    struct prep_norm_t { const float * w = nullptr; float eps = 0.0f; const float * add = nullptr; int64_t ld_add = 0; float * sum = nullptr; int64_t ld_sum = 0;
-                         const float * x_over = nullptr; int64_t ld_over = 0; } prep_norm;
     int64_t     id_calls = 0, id_checked = 0;       // MUL_MAT_ID launches issued / covered by the last look at `flag` (qmm_synchronize reads the word only behind such a launch: a blocking 4-byte copy per synchronize cost llama.cpp's token loop ~70 us per token)
     int64_t     mfma_calls = 0, mfma_checked = 0;   // prefill calls issued / covered by the last non-finite check (qmm_synchronize)
     bool        wide_attr_set = false;

@@ -1,8 +1,9 @@
 // qmm_prefill_plan.h — the one launch plan of the prefill (N > QMM_MATVEC_MAX_N) path: for a weight type, the shapes of a run and
 // the context's switches it decides the kernel with its template arguments, grid, block and LDS bytes, the split-K factor, the
 // operand layout, the activation prep and its key, whether a run of matrices is one launch, and the workspace layout.  Plain C++
-// (no HIP, no ggml; a host compiler alone reads it, like qmm_switches.h).  The launchers (qmm_mfma.hiph, qmm_mfma_regb.hiph,
-// qmm_moe.hiph, mul_mat_group_impl) execute a plan and decide nothing; only what depends on pointers stays with them.
+// (no HIP, no ggml; a host compiler alone reads it, like qmm_switches.h).  prefill_group_plan lists the launches of a whole
+// qmm_mul_mat_group call: its runs, which of them prepare the operand, and the call's workspace.  The launchers (qmm_prefill.hiph,
+// qmm_moe.hiph) execute a plan and decide nothing; only what depends on pointers stays with them.
 #pragma once
 
 #include "../../include/ggml_mi355x_qmm.h"
@@ -13,7 +14,7 @@
 
 namespace qmm {
 
-// what the decision reads from the context (prefill_rules() in qmm_mfma.hiph fills it from qmm_ctx)
+// what the decision reads from the context (prefill_rules() in qmm_prefill.hiph fills it from qmm_ctx)
 struct PrefillRules {
     int     cus, prec;
     int     skinny, skinny_max_n, skinny_max_n_few;
@@ -30,8 +31,8 @@ enum PrefillKernel { PK_NONE, PK_LDS_TILE, PK_SKINNY, PK_REGB, PK_WIDE, PK_R64_4
                      PK_Q8X };         // QMM_PREC_Q8_EXACT: mfma_q8x_kernel<T> (qmm_mfma_q8x.hiph)
 
 struct PrefillPlan {
-    // a run of 2..4 matrices that cannot be one launch: the caller plans and runs each matrix on its own (the first prepares the
-    // operand); of this plan only the prep fields (the same for every matrix of a run: one key) and ws_total (the largest) count
+    // a run of 2..4 matrices that cannot be one launch: prefill_group_plan lists each matrix with a plan of its own (the first prepares
+    // the operand); of this plan only the prep fields (the same for every matrix of a run: one key) and ws_total (the largest) count
     bool     per_matrix;
     // the MFMA launch.  ta / tb: mfma_kernel<T, ta>, mfma_skinny_kernel<T, ta, tb>, mfma_regb_kernel<T, ta, tb> (Q4_K: mfma_regb_q4k_kernel<ta, tb>)
     int      kernel, ta, tb;
@@ -251,7 +252,7 @@ inline PrefillPlan plan_q8x(int type, const int64_t * M, int n, int64_t K, int64
 
 } // namespace plan_detail
 
-// the prep key of one matrix alone: mul_mat_group_impl cuts a group into runs of one type and one key
+// the prep key of one matrix alone: prefill_group_plan cuts a group into runs of one type and one key
 inline int prefill_prep_key(const PrefillRules & r0, int type, int64_t M, int64_t K, int64_t N) {
     const PrefillRules r = prefill_effective_rules(r0, type, K, false);
     if (r.prec == QMM_PREC_Q8_EXACT) return Q8X_KEY;
@@ -312,6 +313,47 @@ inline PrefillPlan prefill_plan(const PrefillRules & r0, int type, const int64_t
         p.ws_total = off + (p.ksplit > 1 ? (size_t) p.ksplit * N * p.mtot * sizeof(float) : 0) + 256;
     }
     return p;
+}
+
+// The launches of one plain MUL_MAT group call (nw matrices on one src1 of N > QMM_MATVEC_MAX_N tokens), in issue order on one stream.
+// An entry is one MFMA launch (with its reduce) over matrices first .. first + n - 1 of the group, behind the activation prep of its
+// plan when `prep` is set; otherwise it reads the operand the entry before it left in the workspace (same key = same bytes).
+//   - matrices without rows are skipped;
+//   - a run is up to 4 adjacent matrices of one type; if a member's prep key differs from the first's, the first matrix alone;
+//   - a run whose plan is per_matrix becomes one entry per matrix, each planned alone with the same flags;
+//   - an entry prepares unless the entry before it has its key (keys A, B, A: three preps; all entries share the workspace from its start);
+//   - more than PREFILL_MAX_RUNS runs (counted before per_matrix runs expand) are refused: `error` is the message, nothing is listed.
+// ws_total: the largest of the entries' plans, what the call needs before its first launch.
+constexpr int PREFILL_MAX_RUNS = 8;
+struct PrefillEntry { int first, n; bool prep; PrefillPlan plan; };
+struct PrefillGroupPlan {
+    int          n;
+    size_t       ws_total;
+    const char * error;
+    PrefillEntry e[PREFILL_MAX_RUNS * 4];
+};
+
+inline void prefill_group_plan(PrefillGroupPlan & g, const PrefillRules & r, const qmm_weight * ws, int nw, int64_t K, int64_t N, unsigned flags) {
+    g.n = 0;  g.ws_total = 0;  g.error = nullptr;
+    int runs = 0, last_key = -1;
+    auto add = [&](int first, int n, const PrefillPlan & p) {
+        g.e[g.n++] = { first, n, p.key != last_key, p };
+        last_key = p.key;
+        if (p.ws_total > g.ws_total) g.ws_total = p.ws_total;
+    };
+    for (int i = 0; i < nw;) {
+        if (ws[i].M == 0) { ++i; continue; }
+        int64_t M[4] = { ws[i].M };
+        const int key = prefill_prep_key(r, ws[i].type, ws[i].M, K, N);
+        int j = i + 1;
+        while (j < nw && j - i < 4 && ws[j].type == ws[i].type && ws[j].M > 0) { M[j - i] = ws[j].M; ++j; }
+        for (int k = i + 1; k < j; ++k) if (prefill_prep_key(r, ws[k].type, ws[k].M, K, N) != key) j = i + 1;
+        if (runs++ == PREFILL_MAX_RUNS) { g.n = 0;  g.ws_total = 0;  g.error = "too many runs in one group";  return; }
+        const PrefillPlan p = prefill_plan(r, ws[i].type, M, j - i, K, N, 1, flags);
+        if (!p.per_matrix) add(i, j - i, p);
+        else for (int k = i; k < j; ++k) add(k, 1, prefill_plan(r, ws[i].type, M + (k - i), 1, K, N, 1, flags));
+        i = j;
+    }
 }
 
 } // namespace qmm

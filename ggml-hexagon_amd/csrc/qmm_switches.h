@@ -31,7 +31,6 @@
     X(R64,                  ATOI,    2, "[lib] Q4_K prefill through the 64-rows-per-wave kernel: bit 0 = for 256 x 128, bit 1 = for 256 x 256") \
     X(R64S,                 ATOI,    1, "[lib] 0 = the compiler-scheduled 64-rows-per-wave kernel instead of the hand-placed one")  \
     X(PREP_REG,             ATOI,    1, "[lib] 0 = the LDS-staged activation prep for Q8_K rows too")                                \
-    X(SIDE,                 ATOI,    0, "[lib] 1 = side streams for a prefill group's second weight format (measured no faster)")   \
     X(ABLATE,               ATOI,    0, "[lib] development ablation word of the MFMA kernels (g_mfma_dbg); written only when set") \
     X(ATTN_SHORT,           OFF0,    1, "[lib] 0 = the general few-token attention kernel at every cache length")                    \
     X(ATTN_SPLIT,           OFF0,    1, "[lib] 0 = no split of long KV ranges over workgroups in the few-token attention")          \

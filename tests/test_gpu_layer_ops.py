@@ -87,12 +87,13 @@ def test_prefill_group_with_residual_add_and_norm(qmm, oracle, n):
     """qmm_mul_mat_group_ex at prompt batch sizes (round 3): the activation prep forms rms_norm(x + add) * w itself and stores x + add; against
     the launches it replaces (the add, the norm, then the plain group): the sum bit for bit, the products within the prefill bar of each
     other and of the oracle fed with the numpy-normed rows.  A same-type group, q / k / v with a Q6_K matrix (one prep for both operand
-    orders' shared bytes), Q5_K + Q3_K, without the add, the sum stored over x (ggml-alloc's in-place add)"""
+    orders' shared bytes), Q5_K + Q3_K, without the add, the sum stored over x (ggml-alloc's in-place add), the same with three preps"""
     import ggml_hexagon_amd.synth as synth
     from oracle.pyoracle import Q3_K, Q5_K
     rng = np.random.default_rng(300 + n)
     for k, spec, with_add, in_place in ((4096, ((Q4_K, 320), (Q4_K, 64)), True, False), (4096, ((Q4_K, 256), (Q4_K, 96), (Q6_K, 128)), True, True),
-                                        (2048, ((Q5_K, 130), (Q3_K, 70)), True, False), (1024, ((Q4_K, 200),), False, False)):
+                                        (2048, ((Q5_K, 130), (Q3_K, 70)), True, False), (1024, ((Q4_K, 200),), False, False),
+                                        (4096, ((Q4_K, 256), (Q6_K, 128), (Q4_K, 96)), True, True)):     # prep keys A, B, A: two later preps read the stored sum
         x0 = rng.normal(0, 1.5, (n, k)).astype(np.float32)
         b0 = rng.normal(0, 1.0, (n, k)).astype(np.float32)
         w = rng.normal(1, 0.1, k).astype(np.float32)
@@ -104,6 +105,8 @@ def test_prefill_group_with_residual_add_and_norm(qmm, oracle, n):
         outs = [torch.zeros((n, a.shape[0]), device="cuda") for _, a in ws_np]
         labels = qmm.trace(lambda: qmm.mul_mat_group_ex(ws, k, x, outs, norm_w=dw, eps=eps, norm_add=b if with_add else None, norm_sum=s_fused if with_add else None))
         assert any("norm" in l for l in labels) and not any(l.startswith("prep_act_q8k_kernel<") and "norm" not in l for l in labels), labels
+        if n == 33 and [t for t, _ in spec] == [Q4_K, Q6_K, Q4_K]:
+            assert sum(l.startswith("prep_act") for l in labels) == 3, labels
         # the launches it replaces
         x2 = dev(x0)
         xs = x2 + b if with_add else x2

@@ -253,6 +253,39 @@ def test_prefill_group_one_tiled_launch(qmm, oracle, t):
             assert torch.equal(o, qmm.mul_mat(t, wd, k, dev(x)))
 
 
+@pytest.mark.parametrize("n", [33, 200])
+def test_prefill_group_prep_keys_a_b_a(qmm, n):
+    """a prompt-batch group whose activation-prep keys go A, B, A (Q4_K, Q4_0, Q4_K): an entry re-uses the operand only of the entry
+    right before it, so the third matrix prepares again; every output identical to the matrix's own single call"""
+    import ggml_hexagon_amd.synth as synth
+    k = 1024
+    ws = [(t, dev(synth.synth_weights(t, m, k, seed=m + t, sigma=0.25))) for t, m in ((Q4_K, 256), (Q4_0, 128), (Q4_K, 96))]
+    x = dev(np.random.default_rng(k + n).uniform(-1, 1, (n, k)).astype(np.float32))
+    outs = [torch.full((n, w.shape[0]), 3.0, device="cuda") for _, w in ws]
+    labels = qmm.trace(lambda: qmm.mul_mat_group(ws, k, x, outs))
+    if n == 33:
+        assert tuple(l for l in labels if l.startswith("prep_act")) == ("prep_act_q8k_kernel<2>", "prep_act_kernel<8>", "prep_act_q8k_kernel<2>"), labels
+    for (t, w), o in zip(ws, outs):
+        assert torch.equal(o, qmm.mul_mat(t, w, k, x)), (TYPE_NAMES[t], n)
+
+
+def test_prefill_group_one_type_cut_by_prep_key(qmm):
+    """two Q4_K matrices at 100 tokens on a 256-CU chip: the large one runs the tiled kernel (row-major operand), the small one the
+    few-token kernel (fragment-major operand): two runs of one matrix, a prep each; outputs identical to the single calls"""
+    import ggml_hexagon_amd.synth as synth
+    if torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        pytest.skip("the shapes put the two matrices on different kernels on a 256-CU device only")
+    k, n = 1024, 100
+    ws = [(Q4_K, dev(synth.synth_weights(Q4_K, m, k, seed=m, sigma=0.25))) for m in (8224, 96)]
+    x = dev(np.random.default_rng(k + n).uniform(-1, 1, (n, k)).astype(np.float32))
+    outs = [torch.full((n, w.shape[0]), 3.0, device="cuda") for _, w in ws]
+    labels = qmm.trace(lambda: qmm.mul_mat_group(ws, k, x, outs))
+    kinds = [l.split("_kernel")[0] for l in labels if l.startswith(("prep_act", "mfma_"))]
+    assert kinds == ["prep_act_q8k", "mfma_regb", "prep_act_q8k", "mfma_skinny"], labels
+    for (t, w), o in zip(ws, outs):
+        assert torch.equal(o, qmm.mul_mat(t, w, k, x))
+
+
 # ----------------------------------------------------------------------------- MFMA path (N > 8)
 
 @pytest.mark.parametrize("t", ALL, ids=IDS)

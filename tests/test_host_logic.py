@@ -333,7 +333,7 @@ SWITCH_HEADER = ROOT / "ggml-hexagon_amd" / "csrc" / "qmm_switches.h"
 SWITCH_DEFAULTS = {
     "PREC": ("STR", None), "ACT_MODE": ("ATOI", 0), "SPLITK": ("ATOI", 1), "SPLITK_COMBINE": ("ATOI", 0), "SKINNY": ("ATOI", 1),
     "SKINNY_MAXN": ("ATOI", 0), "MM_GROUP": ("ATOI", 1), "MV_KMIX": ("ATOI", 2), "MV_BPC": ("ATOI", 1), "MV_ONEPASS": ("ATOI", 1),
-    "REGB_Q23": ("ATOI", 1), "WIDE": ("ATOI", 1), "R64": ("ATOI", 2), "R64S": ("ATOI", 1), "PREP_REG": ("ATOI", 1), "SIDE": ("ATOI", 0),
+    "REGB_Q23": ("ATOI", 1), "WIDE": ("ATOI", 1), "R64": ("ATOI", 2), "R64S": ("ATOI", 1), "PREP_REG": ("ATOI", 1),
     "ABLATE": ("ATOI", 0), "ATTN_SHORT": ("OFF0", 1), "ATTN_SPLIT": ("OFF0", 1), "RCCL_LIB": ("STR", None), "CHAIN": ("ATOI", 0),
     "GLUE": ("OFF0", 1), "FUSE": ("OFF0", 1), "ATTN_ROPE": ("OFF0", 1), "REPACK": ("OFF0", 1), "STAGED_SET": ("OFF0", 1),
     "RCCL": ("ATOI", 0), "TIMING": ("ATOI", 0), "NO_PINNED": ("PRESENT", 0), "DEBUG": ("PRESENT", 0), "VIRTUAL_DEVICES": ("STR", None),
@@ -379,7 +379,7 @@ def switch_probe(tmp_path_factory):
 
 def test_switch_table_keeps_every_name_kind_and_default(switch_probe):
     table = switch_probe(table=True)
-    assert len(table) == 36 and set(table) == set(SWITCH_DEFAULTS)
+    assert len(table) == 35 and set(table) == set(SWITCH_DEFAULTS)
     unset = switch_probe()
     for name, (kind, default) in SWITCH_DEFAULTS.items():
         assert table[name][0] == kind, name
@@ -623,6 +623,179 @@ def test_prefill_rules_live_in_the_plan_header_only():
         for n, line in enumerate(f.read_text().splitlines(), 1):
             code = re.sub(r"//.*$", "", line)
             assert not re.search(r"\b(mfma_use_skinny|mfma_use_wide|mfma_splitk)\b", code), f"{f.name}:{n}: {line.strip()[:120]}"
+
+
+# ---- the group plan (prefill_group_plan of the same header): the launches of a whole qmm_mul_mat_group call at a prompt batch
+
+GROUP_PROBE = r"""
+#include "qmm_prefill_plan.h"
+#include <cstdlib>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+using namespace qmm;
+int main() {
+    std::string spec;
+    while (std::getline(std::cin, spec)) {          // cus type1,type2,.. M1,M2,.. K N flags [NAME=VAL ...]
+        std::istringstream in(spec);
+        PrefillRules r = { 256, QMM_PREC_F16_Q8, 1, 64, 128, 1, 0, 1 << 16, 1, 2, 1, 1, 1, 1 };      // qmm_ctx's defaults
+        unsigned flags; int64_t K, N; std::string ts, ms, kv;
+        in >> r.cus >> ts >> ms >> K >> N >> flags;
+        std::vector<qmm_weight> ws;
+        { std::istringstream t(ts), m(ms); std::string x, y;
+          while (std::getline(t, x, ',') && std::getline(m, y, ',')) { qmm_weight w = {}; w.type = atoi(x.c_str()); w.M = atoll(y.c_str()); ws.push_back(w); } }
+        while (in >> kv) {
+            const std::string name = kv.substr(0, kv.find('=')); const int v = atoi(kv.c_str() + kv.find('=') + 1);
+            if (name == "R64") r.r64 = v; else if (name == "SPLITK") r.splitk = v; else if (name == "SKINNY") r.skinny = v;
+            else if (name == "SKINNY_MAXN") r.skinny_max_n = r.skinny_max_n_few = v; else if (name == "WIDE") r.wide = v; else if (name == "R64S") r.r64s = v;
+            else if (name == "PREP_REG") r.prep_reg = v; else if (name == "REGB_Q23") r.regb_q23 = v; else if (name == "MM_GROUP") r.mm_group = v;
+            else if (name == "SPLITK_COMBINE") r.splitk_combine = v; else if (name == "BF16") r.prec = v ? QMM_PREC_BF16 : QMM_PREC_F16_Q8;
+            else if (name == "Q8") r.prec = v ? QMM_PREC_Q8_EXACT : QMM_PREC_F16_Q8; else return 1;
+        }
+        PrefillGroupPlan g;
+        prefill_group_plan(g, r, ws.data(), (int) ws.size(), K, N, flags);
+        if (g.error) { printf("refused: %s\n", g.error); continue; }
+        for (int k = 0; k < g.n; ++k) {
+            const PrefillEntry & e = g.e[k];
+            if (e.plan.per_matrix || e.n < 1 || e.n > 4) return 2;
+            printf("%d..%d %s%s %s%s; ", e.first, e.first + e.n - 1, e.plan.label, e.plan.combine_ok ? "+combine" : "", e.prep ? "prep=" : "reuse", e.prep ? e.plan.prep_label : "");
+        }
+        printf("ws=%zu\n", g.ws_total);
+    }
+    return 0;
+}
+"""
+# (group, its launches in issue order).  A group: CUs, the weight type id and the rows of each matrix, K, tokens, flags (2 = SwiGLU input,
+# 4 = fused norm), switches off their defaults (Q8=1: QMM_PREC_Q8_EXACT).  A launch: first..last matrix, the MFMA label, then the prep it
+# goes behind or "reuse" (the operand of the launch before it); last the workspace bytes of the call.
+# The right-hand sides were printed by the code of the commit before prefill_group_plan existed: mul_mat_group_impl's run-cutting loop,
+# its re-use test (side streams off) and mfma_mul_mat's per-matrix recursion, copied into a stand-alone program on that commit's plan
+# header, never by this function: q / k / v as one launch and per matrix, mixed types with one key and with two, one type cut by key,
+# keys A, B, A, rows of zero, more than 4 of a type, 9 and 8 runs, each flag, Q8-exact, other chip sizes, the switches a group meets.
+GROUP_TABLE = [
+    ("256 12,12,12 4096,1024,1024 4096 512 0",
+     "0..2 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; ws=29362432"),
+    ("256 12,12,12 4096,1024,1024 4096 512 0 MM_GROUP=0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 1..1 mfma_regb_kernel<12,8,128> reuse; 2..2 mfma_regb_kernel<12,8,128> reuse; ws=37751040"),
+    ("256 12,12,12 4096,1024,1024 4096 100 0",
+     "0..0 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; 1..1 mfma_skinny_kernel<12,8,2> reuse; 2..2 mfma_skinny_kernel<12,8,2> reuse; ws=1049344"),
+    ("256 12,12,12 4096,1024,1024 4096 9 0",
+     "0..0 mfma_skinny_kernel<12,8,1> prep=prep_act_q8k_kernel<2>; 1..1 mfma_skinny_kernel<12,8,1> reuse; 2..2 mfma_skinny_kernel<12,8,1> reuse; ws=1049344"),
+    ("256 12,12,12 4096,1024,1024 4096 129 0",
+     "0..2 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; ws=17949952"),
+    ("256 12,12,14 4096,1024,1024 4096 512 0",
+     "0..1 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 2..2 mfma_regb_kernel<14,8,128> reuse; ws=35653888"),
+    ("256 12,12,14 4096,1024,1024 4096 33 0",
+     "0..0 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; 1..1 mfma_skinny_kernel<12,8,2> reuse; 2..2 mfma_skinny_kernel<14,8,2> prep=prep_act_q8k_kernel<3>; ws=1049344"),
+    ("256 12,12,14 4096,1024,1024 4096 33 0 SKINNY=0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 1..1 mfma_regb_kernel<12,8,128> reuse; 2..2 mfma_regb_kernel<14,8,128> reuse; ws=5374720"),
+    ("256 12,12 16384,4096 4096 100 0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 1..1 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; ws=27263744"),
+    ("256 12,12 8224,96 1024 100 0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 1..1 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; ws=6842112"),
+    ("304 12,12 8224,96 1024 100 0",
+     "0..0 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; 1..1 mfma_skinny_kernel<12,8,2> reuse; ws=262912"),
+    ("64 12,12 16384,4096 4096 100 0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 1..1 mfma_regb_kernel<12,8,128> reuse; ws=7602944"),
+    ("256 12,2,12 256,128,96 1024 33 0",
+     "0..0 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; 1..1 mfma_skinny_kernel<2,8,2> prep=prep_act_kernel<8>; 2..2 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; ws=262912"),
+    ("256 12,2,12 256,128,96 1024 200 0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 1..1 mfma_regb_kernel<2,8,128> prep=prep_act_kernel<8>; 2..2 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; ws=935168"),
+    ("256 12,12,12 4096,0,1024 4096 512 0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 2..2 mfma_regb_kernel<12,8,128> reuse; ws=37751040"),
+    ("256 12,14,12 4096,0,1024 4096 512 0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 2..2 mfma_regb_kernel<12,8,128> reuse; ws=37751040"),
+    ("256 12,12 0,0 4096 512 0",
+     "ws=0"),
+    ("256 12,12,12,12,12 1024,1024,1024,1024,1024 4096 512 0",
+     "0..3 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 4..4 mfma_regb_kernel<12,8,128> reuse; ws=37751040"),
+    ("256 12,12,12,12,14,14 4096,1024,1024,4096,1024,1024 4096 512 0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 1..1 mfma_regb_kernel<12,8,128> reuse; 2..2 mfma_regb_kernel<12,8,128> reuse; 3..3 mfma_regb_kernel<12,8,128> reuse; 4..5 mfma_regb_kernel<14,8,128> reuse; ws=37751040"),
+    ("256 12,14,12,14,12,14,12,14,12 256,256,256,256,256,256,256,256,256 1024 33 0",
+     "refused: too many runs in one group"),
+    ("256 12,14,12,14,12,14,12,14 256,256,256,256,256,256,256,256 1024 33 0",
+     "0..0 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; 1..1 mfma_skinny_kernel<14,8,2> prep=prep_act_q8k_kernel<3>; 2..2 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; 3..3 mfma_skinny_kernel<14,8,2> prep=prep_act_q8k_kernel<3>; 4..4 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; 5..5 mfma_skinny_kernel<14,8,2> prep=prep_act_q8k_kernel<3>; 6..6 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2>; 7..7 mfma_skinny_kernel<14,8,2> prep=prep_act_q8k_kernel<3>; ws=262912"),
+    ("256 12 4096 14336 512 2",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; ws=48236800"),
+    ("256 14,14 4096,4096 14336 512 2",
+     "0..1 mfma_regb_kernel<14,8,128> prep=prep_act_q8k_kernel<3>; ws=48236800"),
+    ("256 12,12,14 4096,1024,1024 4096 512 4",
+     "0..1 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2,norm>; 2..2 mfma_regb_kernel<14,8,128> reuse; ws=35653888"),
+    ("256 12,14,12 256,128,96 4096 33 4",
+     "0..0 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2,norm>; 1..1 mfma_skinny_kernel<14,8,2> prep=prep_act_q8k_kernel<3,norm>; 2..2 mfma_skinny_kernel<12,8,2> prep=prep_act_q8k_kernel<2,norm>; ws=1049344"),
+    ("256 2,2 4096,4096 4096 512 4",
+     "0..1 mfma_regb_kernel<2,8,128> prep=prep_act_kernel<8>; ws=37751040"),
+    ("256 12,12,12 4096,1024,1024 4096 512 0 Q8=1",
+     "0..0 mfma_q8x_kernel<12> prep=prep_act_q8x_kernel; 1..1 mfma_q8x_kernel<12> reuse; 2..2 mfma_q8x_kernel<12> reuse; ws=2130176"),
+    ("256 12,2,12 4096,1024,1024 4096 512 0 Q8=1",
+     "0..0 mfma_q8x_kernel<12> prep=prep_act_q8x_kernel; 1..1 mfma_regb_kernel<2,8,128> prep=prep_act_kernel<8>; 2..2 mfma_q8x_kernel<12> prep=prep_act_q8x_kernel; ws=20973824"),
+    ("256 12,12,14 4096,1024,1024 4096 33 0 Q8=1",
+     "0..0 mfma_q8x_kernel<12> prep=prep_act_q8x_kernel; 1..1 mfma_q8x_kernel<12> reuse; 2..2 mfma_q8x_kernel<14> reuse; ws=137728"),
+    ("256 12,14 4096,1024 4096 512 4 Q8=1",
+     "0..0 mfma_q8x_kernel<12> prep=prep_act_q8x_kernel; 1..1 mfma_q8x_kernel<14> reuse; ws=2130176"),
+    ("304 12,12,12 4096,1024,1024 4096 512 0",
+     "0..2 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; ws=41945344"),
+    ("64 12,12,14 4096,1024,1024 4096 512 0",
+     "0..1 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 2..2 mfma_regb_kernel<14,8,128> reuse; ws=12585216"),
+    ("256 2,2,2 4096,4096,4096 4096 512 0",
+     "0..0 mfma_regb_kernel<2,8,128> prep=prep_act_kernel<8>; 1..1 mfma_regb_kernel<2,8,128> reuse; 2..2 mfma_regb_kernel<2,8,128> reuse; ws=37751040"),
+    ("256 12,12 14336,14336 4096 512 0",
+     "0..1 mfma_r64s_q4k_kernel<2> prep=prep_act_q8k_kernel<2>; ws=4196608"),
+    ("256 12,12 14336,14336 4096 512 0 R64S=0",
+     "0..1 mfma_r64_q4k_kernel<8> prep=prep_act_q8k_kernel<2>; ws=4196608"),
+    ("256 12,12 14336,14336 4096 512 0 WIDE=0",
+     "0..1 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; ws=4196608"),
+    ("256 12,13 4096,4096 4096 512 0",
+     "0..0 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; 1..1 mfma_regb_kernel<13,8,128> reuse; ws=37751040"),
+    ("256 14,14 4096,1024 4096 512 0 BF16=1",
+     "0..0 mfma_kernel<14,64> prep=prep_act_kernel<15>; 1..1 mfma_kernel<14,64> reuse; ws=4196608"),
+    ("256 12,12,12 4096,1024,1024 4096 512 0 SPLITK_COMBINE=1",
+     "0..2 mfma_regb_kernel<12,8,128>+combine prep=prep_act_q8k_kernel<2>; ws=29362432"),
+    ("256 11,11 4096,1024 4096 512 0 REGB_Q23=0",
+     "0..0 mfma_kernel<11,64> prep=prep_act_q8k_kernel<0>; 1..1 mfma_kernel<11,64> reuse; ws=4196608"),
+    ("256 14 32000 4096 512 0",
+     "0..0 mfma_regb_kernel<14,8,128> prep=prep_act_q8k_kernel<3>; ws=4196608"),
+    ("256 8,8,12 1024,1024,4096 4096 512 0",
+     "0..1 mfma_regb_kernel<8,8,128> prep=prep_act_kernel<8>; 2..2 mfma_regb_kernel<12,8,128> prep=prep_act_q8k_kernel<2>; ws=37751040"),
+]
+
+
+@pytest.fixture(scope="module")
+def group_probe(tmp_path_factory):
+    """the plan header alone, compiled by the host compiler into a program that prints the group plan of each group on its input"""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    d = tmp_path_factory.mktemp("group")
+    (d / "probe.cpp").write_text(GROUP_PROBE)
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", f"-I{PLAN_HEADER.parent}", str(d / "probe.cpp"), "-o", str(d / "probe")], check=True)
+    return lambda specs: subprocess.run([str(d / "probe")], input="\n".join(specs) + "\n", check=True, capture_output=True, text=True).stdout.splitlines()
+
+
+def test_prefill_group_plan_keeps_every_decision(group_probe):
+    assert len(GROUP_TABLE) >= 30
+    got = group_probe([spec for spec, _ in GROUP_TABLE])
+    assert len(got) == len(GROUP_TABLE)
+    for (spec, want), line in zip(GROUP_TABLE, got):
+        assert line == want, spec
+
+
+def test_prefill_group_rules_live_in_the_plan_header_only():
+    """how a group is cut into runs is the plan's own: no other file in csrc/ calls prefill_prep_key (comments may speak of it), and
+    the context has no member through which a prefill call would talk to its callees, nor side streams"""
+    csrc = ROOT / "ggml-hexagon_amd" / "csrc"
+    for f in sorted(csrc.iterdir()):
+        if f == PLAN_HEADER or f.suffix not in (".cpp", ".h", ".hip", ".hiph"):
+            continue
+        for n, line in enumerate(f.read_text().splitlines(), 1):
+            code = re.sub(r"//.*$", "", line)
+            assert not re.search(r"\bprefill_prep_key\b", code), f"{f.name}:{n}: {line.strip()[:120]}"
+    for n, line in enumerate((csrc / "qmm_host.h").read_text().splitlines(), 1):
+        code = re.sub(r"//.*$", "", line)
+        assert not re.search(r"\b(prep_x2|prep_ldx2|prep_norm|ws_base|ws_used|side|side_on)\b", code), f"qmm_host.h:{n}: {line.strip()[:120]}"
 
 
 # ---- the few-token launch plan (csrc/qmm_matvec_plan.h): kernel, instantiation, grid, block and LDS of the N <= 8 mat-vec paths
