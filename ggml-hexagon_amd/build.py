@@ -1,6 +1,7 @@
 """hipcc build recipes (gfx950 only, in-tree outputs so the .so files travel with gpurun snapshots)."""
 from __future__ import annotations
 
+import hashlib
 import os
 import shutil
 import subprocess
@@ -13,8 +14,9 @@ QMM_SO = PKG / "libggml_mi355x_qmm.so"
 PLUGIN_SO = PKG / "libggml-mi355x.so"
 # a copy of the plugin kept with the other binaries built from the ggml tree (oracle/_ref, never in git): a checkout on a
 # machine without that tree takes the module from there.  A directory of its own: next to the reference's executables it
-# would sit where ggml looks for backend modules by name
-PLUGIN_PREBUILT = ROOT / "oracle" / "_ref" / "plugin" / "libggml-mi355x.so"
+# would sit where ggml looks for backend modules by name, and under the fingerprint of the sources it was compiled from (plugin_prebuilt):
+# oracle/_ref outlives a checkout and may serve several commits, and a module of other sources must never stand in for this tree's
+PLUGIN_PREBUILT_DIR = ROOT / "oracle" / "_ref" / "plugin"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 GGML_SRC = Path(os.environ.get("GGML_SRC_DIR", "/root/reference/ggml"))
 
@@ -28,7 +30,7 @@ def _newer(target: Path, sources) -> bool:
 
 def build_qmm(force: bool = False) -> Path:
     """the kernel library behind include/ggml_mi355x_qmm.h and include/ggml_mi355x_ops.h: one object per translation unit
-    (qmm_api.hip = the quantized MUL_MAT path with, as its section qmm_prefill.hiph, the prompt-batch launches, qmm_ops.hip = the glue ops (what they launch: qmm_glue_plan.h) and, as its section qmm_attn.hiph, the attention launches, qmm_comm.hip = the RCCL exchange of a one-process row split), rebuilt only when its sources changed"""
+    (qmm_api.hip = the quantized MUL_MAT path with, as its section qmm_prefill.hiph, the prompt-batch launches, qmm_ops.hip = the glue ops (what they launch: qmm_glue_plan.h) and, as its section qmm_attn.hiph (with qmm_attn_rows.hiph), the attention launches, qmm_comm.hip = the RCCL exchange of a one-process row split), rebuilt only when its sources changed"""
     headers = sorted(CSRC.glob("qmm_*.hiph")) + sorted(CSRC.glob("qmm_*.h")) + sorted((ROOT / "include").glob("ggml_mi355x_*.h"))
     units = [CSRC / "qmm_api.hip", CSRC / "qmm_ops.hip", CSRC / "qmm_comm.hip"]
     if not force and _newer(QMM_SO, units + headers):
@@ -54,21 +56,37 @@ def have_ggml_headers() -> bool:
     return (GGML_SRC / "include" / "ggml-backend.h").exists() and (GGML_SRC / "src" / "ggml-backend-impl.h").exists()
 
 
+def plugin_sources() -> list[Path]:
+    """everything the plugin module is compiled from (one translation unit, ggml-mi355x.cpp, which includes the other sections)"""
+    return [CSRC / "ggml-mi355x.cpp"] + sorted(CSRC.glob("mi355x_*")) + [CSRC / "qmm_switches.h", CSRC / "qmm_matvec_plan.h", CSRC / "qmm_types.h",
+            ROOT / "include" / "ggml-mi355x.h", ROOT / "include" / "ggml_mi355x_qmm.h", ROOT / "include" / "ggml_mi355x_ops.h"]
+
+
+def plugin_prebuilt() -> Path:
+    """where the kept copy of the module built from THIS tree's plugin sources lives: a directory named by the hash of their contents"""
+    h = hashlib.sha256()
+    for f in plugin_sources():
+        h.update(f.name.encode() + b"\0" + f.read_bytes() + b"\0")
+    return PLUGIN_PREBUILT_DIR / h.hexdigest()[:16] / "libggml-mi355x.so"
+
+
 def build_plugin(force: bool = False) -> Path | None:
     """the ggml backend plugin (GGML_BACKEND_DL module).  It is compiled against the ggml headers of the
     llama.cpp tree it will be loaded into (here: the reference tree, in place) and a copy is kept in
-    oracle/_ref/plugin; when that tree is not present the module is taken from that copy (it finds the kernel
-    library next to itself, rpath $ORIGIN), or the module already in place, if any, is kept."""
+    oracle/_ref/plugin/<hash of the plugin sources>; when that tree is not present the module is taken from the copy made from
+    the same sources (it finds the kernel library next to itself, rpath $ORIGIN), or the module already in place, if any, is kept.
+    A copy made from other sources (another commit's) is never used."""
     src = CSRC / "ggml-mi355x.cpp"              # one translation unit: it includes the other sections (mi355x_*.cpp, one per concern)
     if not src.exists():
         return None
-    srcs = [src] + sorted(CSRC.glob("mi355x_*")) + [CSRC / "qmm_switches.h", CSRC / "qmm_matvec_plan.h", CSRC / "qmm_types.h",
-                    ROOT / "include" / "ggml-mi355x.h", ROOT / "include" / "ggml_mi355x_qmm.h", ROOT / "include" / "ggml_mi355x_ops.h"]
+    srcs = plugin_sources()
+    prebuilt = plugin_prebuilt()
     if not force and _newer(PLUGIN_SO, srcs + [QMM_SO]):
         return PLUGIN_SO
     if not have_ggml_headers() or not (shutil.which("g++") or shutil.which("c++")):
-        if PLUGIN_PREBUILT.exists() and (not PLUGIN_SO.exists() or PLUGIN_PREBUILT.stat().st_mtime > PLUGIN_SO.stat().st_mtime):
-            shutil.copy2(PLUGIN_PREBUILT, PLUGIN_SO)
+        # (whatever the dates say: a module left in place by a build of other sources may well be the younger file)
+        if prebuilt.exists() and (not PLUGIN_SO.exists() or prebuilt.read_bytes() != PLUGIN_SO.read_bytes()):
+            shutil.copy2(prebuilt, PLUGIN_SO)
         return PLUGIN_SO if PLUGIN_SO.exists() else None
     cxx = shutil.which("g++") or shutil.which("c++")
     cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-DGGML_BACKEND_DL", "-DGGML_BACKEND_BUILD",
@@ -76,8 +94,8 @@ def build_plugin(force: bool = False) -> Path | None:
            f"-I{GGML_SRC / 'include'}", f"-I{GGML_SRC / 'src'}", f"-I{ROOT / 'include'}",
            str(src), "-o", str(PLUGIN_SO), f"-L{PKG}", "-lggml_mi355x_qmm", "-Wl,-rpath,$ORIGIN"]
     subprocess.run(cmd, check=True)
-    PLUGIN_PREBUILT.parent.mkdir(parents=True, exist_ok=True)
-    shutil.copy2(PLUGIN_SO, PLUGIN_PREBUILT)
+    prebuilt.parent.mkdir(parents=True, exist_ok=True)
+    shutil.copy2(PLUGIN_SO, prebuilt)
     return PLUGIN_SO
 
 

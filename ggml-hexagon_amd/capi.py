@@ -12,6 +12,7 @@ Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, IQ4_NL, IQ4_XS = 3, 6, 7, 10, 11, 20, 23
 ACT_REF, ACT_X86 = 0, 1
 PREC_BF16, PREC_F16_Q8, PREC_Q8_EXACT = 0, 1, 2
 MATVEC_MAX_N = 8
+TENSOR_KV_ROWS = 1      # QMM_TENSOR_KV_ROWS: on the v operand of the attention entry points, V rows are cache positions (FLASH_ATTN_EXT)
 
 EXPORTS = [
     "qmm_abi_version", "qmm_last_error", "qmm_device_count", "qmm_create", "qmm_destroy", "qmm_device", "qmm_stream",
@@ -41,7 +42,7 @@ class QmmTensor(C.Structure):
                 ("op_params", C.c_int32 * 16)]
 
     @classmethod
-    def make(cls, type_, ne, nb=None, data=0, op_params=()):
+    def make(cls, type_, ne, nb=None, data=0, op_params=(), flags=0):
         es = {0: 4, 1: 2, 26: 4}.get(type_, 1)
         ne = list(ne) + [1] * (4 - len(ne))
         if nb is None:
@@ -50,12 +51,26 @@ class QmmTensor(C.Structure):
                 nb.append(acc)
                 acc *= n
         t = cls()
-        t.data, t.type, t.flags = data, type_, 0
+        t.data, t.type, t.flags = data, type_, flags
         t.ne[:] = ne
         t.nb[:] = list(nb)
         for i, v in enumerate(op_params):
             t.op_params[i] = v
         return t
+
+
+def flash_attn_operands(d, n_tok, h, hk, n_kv, *, q=0, k=0, v=0, mask=0, dst=0, q_nb=None, k_nb=None, v_nb=None, mask_type=1, mask_rows=None,
+                        dst_nb1=None):
+    """the five descriptors of GGML_OP_FLASH_ATTN_EXT as qmm_attn_decode / qmm_attn_prefill take them (include/ggml_mi355x_ops.h): q f32
+    [d, n_tok, h], k / v f16 [d, n_kv, hk] with QMM_TENSOR_KV_ROWS on v, mask f16 (mask_type 1) or f32 (0) [n_kv, mask_rows], dst f32
+    [d * h, n_tok].  Contiguous unless byte strides (nb[0..2]) are given; the keyword pointers are device addresses"""
+    nb4 = lambda nb, last: None if nb is None else list(nb) + [last]
+    tq = QmmTensor.make(0, [d, n_tok, h], nb=nb4(q_nb, 4 * d * n_tok * h), data=q)
+    tk = QmmTensor.make(1, [d, n_kv, hk], nb=nb4(k_nb, 2 * d * n_kv * hk), data=k)
+    tv = QmmTensor.make(1, [d, n_kv, hk], nb=nb4(v_nb, 2 * d * n_kv * hk), data=v, flags=TENSOR_KV_ROWS)
+    tm = QmmTensor.make(mask_type, [n_kv, n_tok if mask_rows is None else mask_rows], data=mask)
+    td = QmmTensor.make(0, [d * h, n_tok], nb=None if dst_nb1 is None else [4, dst_nb1, dst_nb1 * n_tok, dst_nb1 * n_tok], data=dst)
+    return tq, tk, tv, tm, td
 
 
 # enum qmm_op

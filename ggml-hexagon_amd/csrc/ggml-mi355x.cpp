@@ -271,6 +271,7 @@ bool dev_supports_op(ggml_backend_dev_t, const struct ggml_tensor * op) {
             return true;
         case GGML_OP_MUL_MAT:    return glue_op(op) ? supports_glue(op) : supports_mul_mat(op);
         case GGML_OP_MUL_MAT_ID: return supports_mul_mat_id(op);
+        case GGML_OP_FLASH_ATTN_EXT: return supports_flash_attn(op);
         default: return supports_glue(op);
     }
 }

@@ -133,6 +133,47 @@ enum ggml_status compute_glue(mi355x_backend_ctx * ctx, const ggml_tensor * node
     return GGML_STATUS_SUCCESS;
 }
 
+// ---- GGML_OP_FLASH_ATTN_EXT (build_attn_mha with flash attention, src/llama-graph.cpp:1153-1165): q f32 [D, N, H], k / v f16
+// [D, n_kv, H_kv] (v with cache positions as rows: QMM_TENSOR_KV_ROWS), an f16 mask, dst f32 [Dv, H, N] = the merged heads the attention
+// entry points write.  The node goes through those entry points (qmm_attn_decode for up to 8 tokens, qmm_attn_prefill beyond); ALiBi and
+// the soft-cap live in op_params only (the library never sees them) and are refused here, like a missing mask and a quantized or BF16 cache.
+struct flash_attn_operands { qmm_tensor q, k, v, m, d; };
+bool flash_attn_operands_of(const ggml_tensor * node, const mi355x_backend_ctx * ctx, flash_attn_operands & o) {
+    const ggml_tensor * q = node->src[0], * k = node->src[1], * v = node->src[2], * m = node->src[3];
+    if (!q || !k || !v || !m) return false;
+    if (q->type != GGML_TYPE_F32 || k->type != GGML_TYPE_F16 || v->type != GGML_TYPE_F16 || m->type != GGML_TYPE_F16 || node->type != GGML_TYPE_F32) return false;
+    float max_bias, logit_softcap;
+    memcpy(&max_bias, (const float *) node->op_params + 1, sizeof(float));
+    memcpy(&logit_softcap, (const float *) node->op_params + 2, sizeof(float));
+    if (max_bias != 0.0f || logit_softcap != 0.0f) return false;
+    if (q->ne[3] != 1 || k->ne[3] != 1 || v->ne[3] != 1 || m->ne[2] != 1 || m->ne[3] != 1 || node->ne[3] != 1 || !ggml_is_contiguous(node)) return false;
+    o.q = to_qt(q, ctx);  o.k = to_qt(k, ctx);  o.v = to_qt(v, ctx);  o.m = to_qt(m, ctx);  o.d = to_qt(node, ctx);
+    o.v.flags = QMM_TENSOR_KV_ROWS;
+    o.d.ne[0] = node->ne[0] * node->ne[1];  o.d.ne[1] = node->ne[2];  o.d.ne[2] = 1;         // [Dv, H, N] contiguous = [Dv * H, N]
+    o.d.nb[1] = (int64_t) node->nb[2];  o.d.nb[2] = o.d.nb[3] = (int64_t) ggml_nbytes(node);
+    return true;
+}
+
+bool supports_flash_attn(const ggml_tensor * node) {
+    flash_attn_operands o;
+    if (!sw().glue || !flash_attn_operands_of(node, nullptr, o)) return false;
+    return qmm_attn_decode_supported(&o.q, &o.k, &o.v, &o.m, &o.d) || qmm_attn_prefill_supported(&o.q, &o.k, &o.v, &o.m, &o.d);
+}
+
+enum ggml_status compute_flash_attn(mi355x_backend_ctx * ctx, const ggml_tensor * node) {
+    flash_attn_operands o;
+    float scale;
+    memcpy(&scale, node->op_params, sizeof(float));
+    const bool ok = flash_attn_operands_of(node, ctx, o);
+    const bool few = ok && qmm_attn_decode_supported(&o.q, &o.k, &o.v, &o.m, &o.d) != 0;
+    if (!ok || (few ? qmm_attn_decode(ctx->dev->qmm, &o.q, &o.k, &o.v, &o.m, &o.d, scale, qmm_stream(ctx->dev->qmm))
+                    : qmm_attn_prefill(ctx->dev->qmm, &o.q, &o.k, &o.v, &o.m, &o.d, scale, qmm_stream(ctx->dev->qmm)))) {
+        GGML_LOG_ERROR("MI355X FLASH_ATTN_EXT(%s): %s\n", node->name, ok ? qmm_last_error() : "operands outside the offloaded surface");
+        return GGML_STATUS_FAILED;
+    }
+    return GGML_STATUS_SUCCESS;
+}
+
 // Pairs the library runs as one launch: RMS_NORM -> MUL by a one-row weight (build_norm), SILU -> MUL (build_ffn's SwiGLU).
 // Legal only when the first node's result has no other reader: `single_use` is computed per graph in graph_compute.
 int fused_pair(const ggml_tensor * n0, const ggml_tensor * n1, const ggml_tensor ** other) {
@@ -474,7 +515,7 @@ void analyze_readers(mi355x_backend_ctx * ctx, const ggml_cgraph * cgraph) {
             for (int i = 0; i < cgraph->n_nodes; ++i) {
                 const ggml_tensor * n = cgraph->nodes[i];
                 if (is_noop(n)) continue;                                          // a view reads nothing; its readers are found through view_src
-                const bool glue = glue_op(n) != 0;
+                const bool glue = glue_op(n) != 0 || n->op == GGML_OP_FLASH_ATTN_EXT;     // (compute_flash_attn resolves its four operands through to_qt as well)
                 // a quantized 2-D MUL_MAT of this device takes its src1 pointer through to_qt as well (compute_mul_mat)
                 const bool mm_src1 = !glue && n->op == GGML_OP_MUL_MAT && n->src[0] && n->src[1] && !is_split(n->src[0]) && n->src[0]->ne[2] == 1 &&
                                      n->src[0]->ne[3] == 1 && n->src[1]->ne[2] == 1 && n->src[1]->ne[3] == 1;
@@ -996,7 +1037,7 @@ int graph_pass::site_rope_kv_attention(int i, ggml_tensor * node, int gop) {
                        (t->src[0]->view_src ? t->src[0]->view_src : t->src[0])->op == GGML_OP_MUL_MAT && ready(t->src[0]) &&
                        (jk < 0 || t->src[0] != cgraph->nodes[jk])) {
                 jcv = j;
-            } else if (t->op == GGML_OP_MUL_MAT || t->op == GGML_OP_SOFT_MAX) {
+            } else if (t->op == GGML_OP_MUL_MAT || t->op == GGML_OP_SOFT_MAX || t->op == GGML_OP_FLASH_ATTN_EXT) {
                 break;                                                         // attention starts: nothing to find beyond
             }
         }
@@ -1170,6 +1211,8 @@ enum ggml_status graph_compute_once(ggml_backend_t backend, struct ggml_cgraph *
             st = compute_mul_mat(ctx, cgraph->nodes + i, n_nodes - i, done.data() + i);                      // may hoist later MUL_MATs
         } else if (node->op == GGML_OP_MUL_MAT_ID) {
             st = compute_mul_mat_id(ctx, cgraph->nodes + i, n_nodes - i, done.data() + i);
+        } else if (node->op == GGML_OP_FLASH_ATTN_EXT) {
+            st = compute_flash_attn(ctx, node);                                 // opaque to the fusion sites: its own launch
         } else {
             GGML_LOG_ERROR("MI355X: op %s (%s) is outside the offloaded surface\n", ggml_op_name(node->op), node->name);
             st = GGML_STATUS_FAILED;

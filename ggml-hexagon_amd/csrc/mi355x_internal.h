@@ -216,6 +216,7 @@ bool type_supported(enum ggml_type t);
 bool supports_mul_mat(const struct ggml_tensor * op);
 bool supports_mul_mat_id(const struct ggml_tensor * op);
 bool supports_glue(const ggml_tensor * node);
+bool supports_flash_attn(const ggml_tensor * node);
 int  glue_op(const ggml_tensor * node);
 bool group_member(const ggml_tensor * t, const ggml_tensor * b, bool split);
 qmm_tensor to_qt(const ggml_tensor * t, const mi355x_backend_ctx * ctx);

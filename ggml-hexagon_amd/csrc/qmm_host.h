@@ -65,6 +65,7 @@ struct qmm_ctx {
     // The glue labels, one per launch, name the kernel and the branch taken: the table GLUE_LABELS of qmm_glue_plan.h.
     // The attention labels are the plan's (qmm_attn_plan.h), spelled as rocprofv3 prints the kernels:
     //   attn_decode_short_kernel<D,fresh,width>   attn_decode_kernel<D,fresh>   attn_decode_split_kernel<D> then attn_combine_kernel   attn_prefill_kernel<D>
+    //   attn_rows_decode_kernel<D> (a cut cache: then attn_combine_kernel)   attn_rows_prefill_kernel<D>      (QMM_TENSOR_KV_ROWS: FLASH_ATTN_EXT's operands)
     // Untraced, a launch pays one pointer test.
     std::string * trace = nullptr;
 

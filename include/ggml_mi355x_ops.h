@@ -25,11 +25,16 @@ extern "C" {
 typedef struct qmm_tensor {
     void *  data;             /* DEVICE pointer */
     int32_t type;             /* ggml_type: F32 = 0, F16 = 1, I32 = 26, quantized types as in ggml_mi355x_qmm.h */
-    int32_t flags;            /* reserved, 0 */
+    int32_t flags;            /* 0, or QMM_TENSOR_* bits where an entry point names one */
     int64_t ne[4];            /* elements */
     int64_t nb[4];            /* bytes */
     int32_t op_params[16];    /* ggml_tensor::op_params of the node (dst only) */
 } qmm_tensor;
+
+/* qmm_tensor::flags.  QMM_TENSOR_KV_ROWS, on the `v` operand of qmm_attn_decode[_supported] and qmm_attn_prefill[_supported] only:
+ * v's rows are cache positions, as K's are (the V operand of GGML_OP_FLASH_ATTN_EXT), not the transposed cache.  Any other bit, and
+ * this bit on any other operand or entry point, is refused. */
+#define QMM_TENSOR_KV_ROWS 1
 
 enum qmm_op {
     QMM_OP_ADD = 1, QMM_OP_SUB, QMM_OP_MUL, QMM_OP_DIV,
@@ -73,7 +78,15 @@ QMM_API int qmm_op_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * a, const qmm_t
  *   q    f32 [D, N, H]       (any row / head strides)        k  f16 [D, n_kv, H_kv]   rows dense, 16-byte aligned
  *   v    f16 [n_kv, Dv, H_kv] the transposed V cache          mask f32 [n_kv, >= N]
  *   dst  f32 [Dv * H, N]
- * D in {64, 128, 256}, n_kv a multiple of 8 (llama.cpp pads it to 32), H a multiple of H_kv (grouped-query attention). */
+ * D in {64, 128, 256}, n_kv a multiple of 8 (llama.cpp pads it to 32), H a multiple of H_kv (grouped-query attention).
+ *
+ * With v->flags == QMM_TENSOR_KV_ROWS the operands are those of GGML_OP_FLASH_ATTN_EXT on an F16 cache (build_attn_mha with flash
+ * attention, src/llama-graph.cpp:1153-1165; arithmetic of ggml_compute_forward_flash_attn_ext_f16, ggml-cpu.c:10258-10471, with
+ * max_bias = 0 and logit_softcap = 0, sums in f32):
+ *   q    f32 [D, N, H]       (any row / head strides)        k  f16 [D, n_kv, H_kv]   rows dense, 16-byte aligned
+ *   v    f16 [Dv, n_kv, H_kv] rows dense, row and head strides 16-byte aligned, as k
+ *   mask f32 or f16 [n_kv, >= N]                             dst f32 [Dv * H, N]       (the op's [Dv, H, N])
+ * D = Dv in {64, 128}, n_kv a multiple of 64 up to 16384 (llama.cpp pads it to 256 with flash attention), H a multiple of H_kv. */
 QMM_API int qmm_attn_decode_supported(const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
                                       const qmm_tensor * dst);
 QMM_API int qmm_attn_decode(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
@@ -81,7 +94,11 @@ QMM_API int qmm_attn_decode(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tenso
 
 /* The same chain for a prompt batch of any size whose scores fit LDS (n_kv <= 512, a multiple of 32; D = Dv in {64, 128}): one
  * workgroup per (64 tokens, head) keeps the 64 x n_kv score tile in LDS between the two MFMA products, so the f32 score tensor
- * (33 MB per layer at 512 x 512 x 32 heads) never exists.  Same operands and result layout as qmm_attn_decode. */
+ * (33 MB per layer at 512 x 512 x 32 heads) never exists.  Same operands and result layout as qmm_attn_decode.
+ * Longer caches are walked 512 columns at a time with a running maximum and sum per token row.
+ *
+ * With v->flags == QMM_TENSOR_KV_ROWS: the flash-attention operands described at qmm_attn_decode, for any N >= 1; D = Dv in
+ * {64, 128}, n_kv a multiple of 64, q rows and heads 16-byte aligned. */
 QMM_API int qmm_attn_prefill_supported(const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
                                        const qmm_tensor * dst);
 QMM_API int qmm_attn_prefill(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
