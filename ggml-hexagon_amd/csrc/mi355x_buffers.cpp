@@ -65,6 +65,7 @@ int weight_type(mi355x_backend_ctx * ctx, const ggml_tensor * t) {
     // weights only: a quantized tensor in a compute or KV buffer (a Q8_0 K cache) is rewritten all the time; re-laying it
     // in place behind its writers' backs would corrupt it
     if (bc && root->buffer && root->buffer->usage != GGML_BACKEND_BUFFER_USAGE_WEIGHTS) bc = nullptr;
+    if (bf16_weight(root)) bc = nullptr;                          // BF16 rows have no planar form and the library is not asked about them
     int pt = bc ? qmm_planar_type((int) root->type, root->ne[0], (int64_t) root->nb[1]) : 0;
     if (sw().prec_q8 && root->type == GGML_TYPE_Q6_K) pt = 0;     // the Q8-exact prefill reads Q6_K in wire layout: planar rows would run as f16 on Q8
     if (!pt || !ggml_is_contiguous(root) || (uintptr_t) root->data % 16 || t->ne[0] != root->ne[0] || t->nb[1] != root->nb[1]) return dev_type(t);

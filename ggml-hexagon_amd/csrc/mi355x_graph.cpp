@@ -10,8 +10,14 @@ bool type_supported(enum ggml_type t) {
     // the north-star's five formats plus SURVEY 8f-4's (round 2): any stock Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K_* / IQ4_NL GGUF keeps its
     // matmul weights on the device; the kernel library answers the same question through qmm_row_size() != 0
     return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K ||
-           t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K || t == GGML_TYPE_IQ4_NL || t == GGML_TYPE_IQ4_XS;
+           t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K || t == GGML_TYPE_IQ4_NL || t == GGML_TYPE_IQ4_XS ||
+           t == GGML_TYPE_BF16;           // unquantized checkpoints: MUL_MAT only (supports_mul_mat_id refuses it), and no fold takes it (bf16_weight)
 }
+
+// A BF16 weight: the library runs it through kernels of their own (rows of K bf16 values, K in multiples of 32, rows on 16-byte
+// boundaries) that fold no neighbour in.  Every fusion site that would hand a norm, a residual or a SwiGLU to a MUL_MAT group asks
+// this first and leaves the neighbours to their own launches.
+bool bf16_weight(const struct ggml_tensor * w) { return w && w->type == GGML_TYPE_BF16; }
 
 bool is_ours(const struct ggml_tensor * t) {
     ggml_backend_buffer_t b = t->view_src ? t->view_src->buffer : t->buffer;
@@ -25,6 +31,7 @@ bool mul_mat_shape_ok(const struct ggml_tensor * op) {
     if (a->ne[0] % ggml_blck_size(a->type) || a->ne[0] != b->ne[0]) return false;
     if (a->nb[0] != ggml_type_size(a->type) || a->nb[1] < ggml_row_size(a->type, a->ne[0])) return false;
     if (a->nb[1] % 2 || a->nb[2] % 2 || a->nb[3] % 2) return false;
+    if (bf16_weight(a) && (a->ne[0] % 32 || a->nb[1] % 16 || a->nb[2] % 16 || a->nb[3] % 16 || (uintptr_t) a->data % 16)) return false;
     if (b->nb[0] != sizeof(float) || b->nb[1] % 16 || b->nb[2] % 16 || b->nb[3] % 16) return false;
     if (op->nb[0] != sizeof(float) || op->nb[1] % 4 || op->nb[1] < op->ne[0] * sizeof(float)) return false;
     return true;
@@ -43,7 +50,7 @@ bool supports_mul_mat(const struct ggml_tensor * op) {
 
 bool supports_mul_mat_id(const struct ggml_tensor * op) {
     const ggml_tensor * as = op->src[0], * b = op->src[1], * ids = op->src[2];
-    if (!mul_mat_shape_ok(op) || !ids || ids->type != GGML_TYPE_I32) return false;
+    if (!mul_mat_shape_ok(op) || !ids || ids->type != GGML_TYPE_I32 || bf16_weight(as)) return false;
     if (is_split(as)) return false;                                                // as in the reference tree (ggml-cuda.cu:1973)
     if (as->ne[3] != 1 || b->ne[3] != 1 || ids->ne[2] != 1 || ids->ne[3] != 1) return false;
     if (ids->nb[0] != sizeof(int32_t) || ids->nb[1] % 4) return false;
@@ -236,6 +243,9 @@ enum ggml_status compute_mul_mat(mi355x_backend_ctx * ctx, ggml_tensor * const *
             skipped.push_back(d);
         }
         if (dbg()) fprintf(stderr, "group of %d at %s (N=%lld) src1 %s %p -> %p\n", n, dst->name, (long long) N, b->name, b->data, to_qt(b, ctx).data);
+        bool folds = true;                                                     // BF16 matrices take no norm, SwiGLU or residual
+        for (int i = 0; i < n; ++i) folds = folds && ws[i].type != (int) GGML_TYPE_BF16;
+        if (!folds && dbg()) fprintf(stderr, "fusion declined: BF16 weights in the group at %s\n", dst->name);
         const float * x = (const float *) to_qt(b, ctx).data;                  // (a merged-heads CONT may live in the scratch: attention sites)
         int64_t ldx = b->nb[1] / sizeof(float);
         qmm_mv_extra ex{};
@@ -247,14 +257,14 @@ enum ggml_status compute_mul_mat(mi355x_backend_ctx * ctx, ggml_tensor * const *
             ctx->pending_norm = {};
             // the kernels read the un-normed row while they write their results: a result that ggml-alloc placed in the block of
             // that row (dead once the norm has run, in the graph's order) would be overwritten under the staging of other workgroups
-            bool norm_in_kernel = n == pn.readers;
+            bool norm_in_kernel = n == pn.readers && folds;
             for (int i = 0; norm_in_kernel && i < n; ++i)
                 norm_in_kernel = !bytes_overlap(ws[i].dst, (size_t) ((N - 1) * ws[i].ldd + ws[i].M) * sizeof(float), to_qt(pn.rn->src[0], ctx).data, ggml_nbytes(pn.rn->src[0]));
             if (pn.add) {
                 // a prompt batch (site_add_rms_norm held ADD -> RMS_NORM -> MUL back): the group's activation prep adds, norms and stores the
                 // sum.  The products are written by later launches of the same stream, so they may sit on the dead operands; not on the sum
                 const ggml_tensor * x0 = pn.add->src[0], * x1 = pn.add->src[1];
-                norm_in_kernel = n == pn.readers && qmm_mul_mat_group_norm_supported(q, ws, n, K, N);
+                norm_in_kernel = n == pn.readers && folds && qmm_mul_mat_group_norm_supported(q, ws, n, K, N);
                 for (int i = 0; norm_in_kernel && i < n; ++i)
                     norm_in_kernel = !bytes_overlap(ws[i].dst, (size_t) ((N - 1) * ws[i].ldd + ws[i].M) * sizeof(float), to_qt(pn.add, ctx).data, ggml_nbytes(pn.add));
                 if (norm_in_kernel) {
@@ -296,7 +306,7 @@ enum ggml_status compute_mul_mat(mi355x_backend_ctx * ctx, ggml_tensor * const *
         }
         // (c) ffn_gate + ffn_up of a few-token batch whose only readers are silu(gate) and the MUL of the two (build_ffn's SwiGLU):
         //     the kernel pairs the rows and writes the product; neither projection is stored
-        if (n == 2 && N <= QMM_MATVEC_MAX_N && qmm::mv_swiglu_pair(ws[0].type, ws[0].M, ws[1].type, ws[1].M) && !fuse_off()) {
+        if (n == 2 && folds && N <= QMM_MATVEC_MAX_N && qmm::mv_swiglu_pair(ws[0].type, ws[0].M, ws[1].type, ws[1].M) && !fuse_off()) {
             auto uses = [&](const ggml_tensor * t) {
                 auto it = std::lower_bound(ctx->readers.begin(), ctx->readers.end(), t,
                                            [](const mi355x_backend_ctx::reader_info & r, const ggml_tensor * y) { return r.t < y; });
@@ -337,7 +347,7 @@ enum ggml_status compute_mul_mat(mi355x_backend_ctx * ctx, ggml_tensor * const *
         }
         // (b) a lone MUL_MAT whose only reader is the residual ADD right behind it (wo, ffn_down): dst = W x + residual, written
         //     where the ADD would have put it
-        if (n == 1 && N <= QMM_MATVEC_MAX_N && !fuse_off() && !(dst->flags & GGML_TENSOR_FLAG_OUTPUT)) {
+        if (n == 1 && folds && N <= QMM_MATVEC_MAX_N && !fuse_off() && !(dst->flags & GGML_TENSOR_FLAG_OUTPUT)) {
             int j = 1;
             while (j < n_nodes && (done[j] || is_noop(nodes[j]))) ++j;
             const ggml_tensor * add = j < n_nodes ? nodes[j] : nullptr;
@@ -598,6 +608,7 @@ struct graph_pass {
             else if (g.n == 0) break;                                          // something else reads or runs first: keep the graph's order
         }
         g.all = ri && g.n >= 1 && g.n == ri->uses;
+        for (int m = 0; m < g.n; ++m) g.all = g.all && !bf16_weight(cgraph->nodes[g.at[m]]->src[0]);      // no norm is held back for a BF16 group
         return g;
     }
     int site_deferred_silu_mul(int i, ggml_tensor * node, int gop);
@@ -627,7 +638,7 @@ int graph_pass::site_deferred_silu_mul(int i, ggml_tensor * node, int gop) {
             !(node->flags & GGML_TENSOR_FLAG_OUTPUT) && !sw().prec_set) {
             const ggml_tensor * mm = cgraph->nodes[j];
             const qmm_tensor qg = to_qt(gate, ctx), qu = to_qt(up, ctx);      // resolved now: a redirect may expire before node j
-            if (group_member(mm, node, false) && gate->nb[0] == 4 && up->nb[0] == 4 && gate->nb[1] % 16 == 0 && up->nb[1] % 16 == 0 &&
+            if (group_member(mm, node, false) && !bf16_weight(mm->src[0]) && gate->nb[0] == 4 && up->nb[0] == 4 && gate->nb[1] % 16 == 0 && up->nb[1] % 16 == 0 &&
                 (uintptr_t) qg.data % 16 == 0 && (uintptr_t) qu.data % 16 == 0) {
                 ctx->swiglu_in[j] = { (const float *) qg.data, (const float *) qu.data, (int64_t) (gate->nb[1] / 4), (int64_t) (up->nb[1] / 4) };
                 return 1;

@@ -213,6 +213,7 @@ void * hoist_elsewhere(mi355x_backend_ctx * ctx, const ggml_tensor * d);
 
 // ----------------------------------------------------------------------------------------------- mi355x_graph.cpp
 bool type_supported(enum ggml_type t);
+bool bf16_weight(const struct ggml_tensor * w);
 bool supports_mul_mat(const struct ggml_tensor * op);
 bool supports_mul_mat_id(const struct ggml_tensor * op);
 bool supports_glue(const ggml_tensor * node);

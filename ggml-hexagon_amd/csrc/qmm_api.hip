@@ -10,6 +10,7 @@
 #include "qmm_prefill.hiph"           // ... and, behind them, what launches them
 #include "qmm_moe.hiph"
 #include "qmm_chain.hiph"
+#include "qmm_bf16.hiph"              // BF16 weights: kernels, and the executor of qmm_bf16_plan.h
 
 using namespace qmm;
 
@@ -479,6 +480,7 @@ int qmm_synchronize(qmm_ctx * c, void * st) {
 }
 
 size_t qmm_row_size(int type, int64_t k) {
+    if (type == T_BF16) return bf16_row_size(k);
     if (!type_known(type) || k % type_blck(type)) return 0;
     return (size_t) (k / type_blck(type)) * type_tsize(type);
 }
@@ -486,6 +488,13 @@ size_t qmm_row_size(int type, int64_t k) {
 // ------------------------------------------------------------------------------------------- dequantize
 
 int qmm_dequantize(qmm_ctx * c, int type, const void * w, int64_t rb, int64_t rows, int64_t K, float * dst, void * st) {
+    if (c && type == T_BF16) {                                   // the exact f32 widening (qmm_bf16.hiph)
+        const char * why = bf16_weight_refusal(w, rb, K, rows, rows);
+        if (why || (uintptr_t) dst % 16) return fail(QMM_EINVAL, "qmm_dequantize: %s", why ? why : "dst must be 16-byte aligned");
+        HIP_TRY(hipSetDevice(c->device));
+        QMM_CHAIN_FLUSH(c);
+        return run_bf16_widen(c->s(st), w, rb, rows, K, dst);
+    }
     if (!c || !type_known(type)) return fail(QMM_EINVAL, "qmm_dequantize: bad ctx/type %d", type);
     if (K <= 0 || K % type_blck(type)) return fail(QMM_EINVAL, "qmm_dequantize: K=%lld", (long long) K);
     if (rb < (int64_t) qmm_row_size(type, K)) return fail(QMM_EINVAL, "qmm_dequantize: row stride too small");
@@ -559,6 +568,27 @@ static int mul_mat_group_impl(qmm_ctx * c, const qmm_weight * ws, int nw, int64_
                               const qmm_mv_extra * ex, const PrefillInput & in = PrefillInput{}) {
     if (!c || !ws || nw <= 0) return fail(QMM_EINVAL, "qmm_mul_mat_group: bad arguments");
     if (N <= 0) return QMM_OK;
+    int n_bf16 = 0;
+    for (int i = 0; i < nw; ++i) n_bf16 += ws[i].type == T_BF16;
+    if (n_bf16) {
+        // BF16 matrices go to their own plan (qmm_bf16_plan.h) before the quantized machinery sees them: no fold, no chain step, no
+        // precision or activation mode.  A group that mixes them with other types runs as consecutive launches, one per same-kind run.
+        const bool folds = in.flags() || (ex && (ex->norm_w || ex->swiglu || ex->norm_add || ex->residual[0] || ex->residual[1] || ex->residual[2] || ex->residual[3]));
+        if (folds) return fail(QMM_EUNSUPPORTED, "qmm_mul_mat_group: BF16 matrices take no norm, residual or SwiGLU fold");
+        if (n_bf16 < nw) {
+            for (int first = 0, next; first < nw; first = next) {
+                for (next = first + 1; next < nw && (ws[next].type == T_BF16) == (ws[first].type == T_BF16); ++next) {}
+                const int rc = mul_mat_group_impl(c, ws + first, next - first, K, x, N, ldx, stream, nullptr);
+                if (rc) return rc;
+            }
+            return QMM_OK;
+        }
+        const int rc = bf16_check(ws, nw, K, x, N, ldx);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        QMM_CHAIN_FLUSH(c);                                      // inside a recording: what was collected first, then this, directly
+        return run_bf16(c, c->s(stream), ws, nw, K, x, N, ldx);
+    }
     if (ex) {                                                    // few-token extras: validated by the plan header, whatever N
         char msg[160];
         const int rc = matvec_extras_check(ws, nw, K, N, ex, msg, sizeof(msg));
@@ -630,7 +660,9 @@ int qmm_mul_mat_group_norm_supported(qmm_ctx * c, const qmm_weight * ws, int nw,
 
 int qmm_mul_mat_group_ex(qmm_ctx * c, const qmm_weight * ws, int nw, int64_t K, const float * x, int64_t N, int64_t ldx, const qmm_mv_extra * ex,
                          void * stream) {
-    if (c && ex && N > QMM_MATVEC_MAX_N) {
+    bool bf16 = false;
+    for (int i = 0; ws && i < nw; ++i) bf16 = bf16 || ws[i].type == T_BF16;
+    if (c && ex && N > QMM_MATVEC_MAX_N && !bf16) {
         // a prompt batch: only the norm in front of the group (the activation prep forms it); everything else is the few-token kernels'
         if (!ex->norm_w || ex->swiglu || ex->residual[0] || ex->residual[1] || ex->residual[2] || ex->residual[3])
             return fail(QMM_EUNSUPPORTED, "qmm_mul_mat_group_ex: batches of more than %d tokens take the norm only", QMM_MATVEC_MAX_N);

@@ -17,9 +17,13 @@ TYPE_SIZE = {Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q4_1: 20, Q5_0
 NAMES = {Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K",
          Q4_1: "q4_1", Q5_0: "q5_0", Q5_1: "q5_1", Q2_K: "q2_K", Q3_K: "q3_K", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs"}
 BY_NAME = {v: k for k, v in NAMES.items()}
+BF16 = 30                 # no block format: rows of K bf16 values, K in multiples of 32 (the library's surface)
 
 
 def row_size(t: int, k: int) -> int:
+    if t == BF16:
+        assert k % 32 == 0
+        return 2 * k
     assert k % BLCK[t] == 0
     return k // BLCK[t] * TYPE_SIZE[t]
 
@@ -63,6 +67,19 @@ def synth_weights(t: int, rows: int, k: int, seed: int = 0, sigma: float = 0.02)
     else:
         raise ValueError(t)
     return blk.reshape(rows, -1)
+
+
+def f32_to_bf16(x: np.ndarray) -> np.ndarray:
+    """uint16 bits of x rounded to bf16, nearest even (ggml_compute_fp32_to_bf16 for finite values)"""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+def synth_weights_bf16(rows: int, k: int, seed: int = 0, sigma: float = 0.02) -> np.ndarray:
+    """uint16 [rows, k]: N(0, sigma) model weights rounded to bf16 (view as uint8 for the [rows, row_size] wire form)"""
+    assert k % 32 == 0
+    rng = np.random.default_rng(seed)
+    return f32_to_bf16((rng.standard_normal((rows, k)) * sigma).astype(np.float32))
 
 
 def _f16_val(rng, n, scale):

@@ -27,6 +27,7 @@
  *     Calls are asynchronous on that stream; nothing synchronizes except qmm_synchronize / qmm_memcpy_h2d/_d2h;
  *   - `type` is ggml's enum ggml_type value: Q4_0=2, Q8_0=8, Q4_K=12, Q5_K=13, Q6_K=14 (the north-star's five) and, SURVEY 8f-4,
  *     Q4_1=3, Q5_0=6, Q5_1=7, Q2_K=10, Q3_K=11, IQ4_NL=20 (ggml/src/ggml-common.h:174-207, 253-277, 405-410);
+ *     BF16=30 for qmm_mul_mat, qmm_mul_mat_group[_ex], qmm_row_size and qmm_dequantize only (below: "BF16 weights");
  *   - weights are in GGUF wire layout: rows of blocks, `w_row_bytes` apart (>= K/blck*type_size);
  *   - returns 0 on success, a negative QMM_E* code otherwise (qmm_last_error() has the text, per thread).
  *     Nothing falls back to the CPU;
@@ -34,6 +35,17 @@
  *     calls from one thread and on one stream at a time.  The workspace grows on demand, which synchronizes the
  *     device: run a shape once before capturing it into a hipGraph.  Several contexts per device are fine (the
  *     plugin's logical devices each have their own).
+ *
+ * BF16 weights (type 30): rows of K bf16 values (w_row_bytes >= 2 K), the base address and the row stride multiples of 16 bytes, K a
+ *   multiple of 32, M >= 1, N >= 1, ldx >= K and ldd >= M with the alignment rules of the quantized types on x; anything else is refused
+ *   with a message.  Arithmetic: the CPU backend's (vec_dot_type of BF16 is BF16, ggml_vec_dot_bf16): src1 rounded to bf16 as
+ *   ggml_compute_fp32_to_bf16 does (nearest even, subnormals kept), the weights' 16 bits as they are, products and sums in f32; nothing is
+ *   Q8-quantized and nothing passes through f16.  The result does not depend on qmm_set_precision or qmm_set_act_mode, and the same call
+ *   gives the same bits every time (no float atomics, no split-K).  N <= QMM_MATVEC_MAX_N: a streaming mat-vec, up to 4 BF16 matrices of
+ *   a group in one launch; above: v_mfma_f32_32x32x16_bf16 on the weights' bits.  A group that mixes BF16 with other types runs as
+ *   consecutive launches, one per run of matrices of the same kind.  QMM_EUNSUPPORTED for type 30: qmm_mul_mat_group_ex with a norm, a
+ *   residual, a SwiGLU or norm_add, qmm_mul_mat_swiglu_in, qmm_mul_mat_id*; qmm_planar_type, qmm_q8_exact_supported and
+ *   qmm_mul_mat_group_norm_supported return 0; inside a chain recording a BF16 group launches what was recorded and then itself, directly.
  */
 #ifndef GGML_MI355X_QMM_H
 #define GGML_MI355X_QMM_H
@@ -128,6 +140,7 @@ QMM_API int          qmm_event_record(qmm_ctx * ctx, qmm_event * ev, void * stre
 QMM_API int          qmm_stream_wait_event(qmm_ctx * ctx, void * stream, qmm_event * ev);
 QMM_API int          qmm_event_synchronize(qmm_ctx * ctx, qmm_event * ev);              /* host waits for the event */
 
+/* bytes of one weight row of k values; 0 for a type that is no weight type or a k off its block size (BF16: 2 k, k a multiple of 32) */
 QMM_API size_t       qmm_row_size(int type, int64_t k);
 
 /* Planar rows (weight repack at set_tensor; precedent ggml_backend_amx_buffer_set_tensor, ggml/src/ggml-cpu/amx/amx.cpp,
@@ -141,7 +154,7 @@ QMM_API size_t       qmm_row_size(int type, int64_t k);
 QMM_API int qmm_planar_type(int type, int64_t K, int64_t w_row_bytes);
 QMM_API int qmm_repack_rows(qmm_ctx * ctx, int type, void * w, int64_t w_row_bytes, int64_t rows, int64_t K, int to_planar, void * stream);
 
-/* dst f32 [rows, K] (contiguous) = bit-exact unpack of `rows` weight rows */
+/* dst f32 [rows, K] (contiguous) = bit-exact unpack of `rows` weight rows (BF16: the exact f32 widening) */
 QMM_API int qmm_dequantize(qmm_ctx * ctx, int type, const void * w, int64_t w_row_bytes,
                            int64_t rows, int64_t K, float * dst, void * stream);
 
