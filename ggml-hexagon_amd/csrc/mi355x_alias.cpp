@@ -49,9 +49,8 @@ bool can_hoist(const ggml_tensor * t, const std::vector<const ggml_tensor *> & s
 // output.  Returns NULL when it is not.
 void * hoist_elsewhere(mi355x_backend_ctx * ctx, const ggml_tensor * d) {
     if (d->flags & GGML_TENSOR_FLAG_OUTPUT) return nullptr;
-    auto it = std::lower_bound(ctx->readers.begin(), ctx->readers.end(), d,
-                               [](const mi355x_backend_ctx::reader_info & x, const ggml_tensor * y) { return x.t < y; });
-    if (it == ctx->readers.end() || it->t != d || !it->glue_only || it->uses == 0) return nullptr;
+    const auto * it = find_reader(ctx, d);
+    if (!it || !it->glue_only || it->uses == 0) return nullptr;
     const size_t bytes = (ggml_nbytes(d) + 255) & ~(size_t) 255;
     if (ctx->hoist_used + bytes > ctx->hoist_bytes) {
         if (ctx->hoist_used || !ctx->redirects.empty()) {                              // live results in the old block: not this time

@@ -1,5 +1,5 @@
-// mi355x_graph.cpp — the graph pass: which ops the device takes, the reader analysis, the fusion sites, the MUL_MAT / MUL_MAT_ID
-// groups, the glue ops, graph_compute.
+// mi355x_graph.cpp — the graph pass: which ops the device takes, the reader analysis, the fusion sites, the glue ops, graph_compute
+// (the MUL_MAT / MUL_MAT_ID launches themselves: mi355x_mulmat.cpp).
 #include "mi355x_internal.h"
 
 namespace mi355x {
@@ -196,294 +196,6 @@ int fused_pair(const ggml_tensor * n0, const ggml_tensor * n1, const ggml_tensor
 }
 
 
-// Is `t` a quantized MUL_MAT of the group that reads the activation `b` as src1 (wq / wk / wv, ffn_gate / ffn_up)?  The one test the
-// fusion sites, compute_mul_mat and the row-split group share.  `split` picks the kind of weight: false = an ordinary 2-D weight of
-// this device's buffer type; true = a row-split weight (compute_mul_mat_split_group: quantized by dev_supports_op's gate, 2-D by
-// split_buffer_init_tensor, so the split buffer type itself stands in for the other conditions).
-bool group_member(const ggml_tensor * t, const ggml_tensor * b, bool split) {
-    if (t->op != GGML_OP_MUL_MAT || t->src[1] != b) return false;
-    const ggml_tensor * w = t->src[0];
-    if (split) return is_split(w) && supports_mul_mat(t);
-    return !glue_op(t) && supports_mul_mat(t) && is_ours(w) && !is_split(w) && w->ne[2] == 1 && w->ne[3] == 1;
-}
-
-// nodes[0] is the MUL_MAT to run; done[] (parallel to nodes) marks later nodes this call has executed as part of its group
-enum ggml_status compute_mul_mat(mi355x_backend_ctx * ctx, ggml_tensor * const * nodes, int n_nodes, char * done) {
-    const ggml_tensor * dst = nodes[0];
-    const ggml_tensor * a = dst->src[0], * b = dst->src[1];
-    qmm_ctx * q = ctx->dev->qmm;
-    void * st = qmm_stream(q);
-    if (is_split(a)) return compute_mul_mat_split_group(ctx, nodes, n_nodes, done);
-    const int64_t K = a->ne[0], N = b->ne[1];
-    const bool flat = a->ne[2] == 1 && a->ne[3] == 1 && b->ne[2] == 1 && b->ne[3] == 1;
-    if (flat) {
-        // Group the MUL_MAT nodes that read the same src1 (wq/wk/wv, ffn gate/up): batch <= 8: one launch per weight type (or
-        // one mixed-type launch); larger batches: the 16-bit activation operand is prepared once per group.  In llama.cpp's
-        // graph order they are not neighbours (q, rope(q), k, rope(k), v; gate, silu, up), so the scan looks past other
-        // nodes and hoists a later MUL_MAT when that is safe (can_hoist).
-        qmm_weight ws[4];
-        int n = 0, member[4] = { 0, 0, 0, 0 };                                 // node index (relative) of every matrix of the group
-        ws[n++] = qmm_weight{ a->data, (int64_t) a->nb[1], a->ne[1], (float *) dst->data, (int64_t) (dst->nb[1] / sizeof(float)), weight_type(ctx, a) };
-        std::vector<const ggml_tensor *> & skipped = ctx->skipped;
-        skipped.clear();
-        for (int i = 1; i < n_nodes && i <= LOOKAHEAD && n < 4 && !fuse_off(); ++i) {
-            const ggml_tensor * d = nodes[i];
-            if (done[i] || is_noop(d)) continue;
-            const ggml_tensor * w = d->src[0];
-            if (group_member(d, b, false) && w->ne[0] == K) {
-                float * out = (float *) d->data;
-                if (!can_hoist(d, skipped)) out = (float *) hoist_elsewhere(ctx, d);   // its block is still in use here: compute into scratch
-                if (out) {
-                    member[n] = i;
-                    ws[n++] = qmm_weight{ w->data, (int64_t) w->nb[1], w->ne[1], out, (int64_t) (d->nb[1] / sizeof(float)), weight_type(ctx, w) };
-                    done[i] = 1;
-                    continue;
-                }
-            }
-            skipped.push_back(d);
-        }
-        if (dbg()) fprintf(stderr, "group of %d at %s (N=%lld) src1 %s %p -> %p\n", n, dst->name, (long long) N, b->name, b->data, to_qt(b, ctx).data);
-        bool folds = true;                                                     // BF16 matrices take no norm, SwiGLU or residual
-        for (int i = 0; i < n; ++i) folds = folds && ws[i].type != (int) GGML_TYPE_BF16;
-        if (!folds && dbg()) fprintf(stderr, "fusion declined: BF16 weights in the group at %s\n", dst->name);
-        const float * x = (const float *) to_qt(b, ctx).data;                  // (a merged-heads CONT may live in the scratch: attention sites)
-        int64_t ldx = b->nb[1] / sizeof(float);
-        qmm_mv_extra ex{};
-        bool use_ex = false;
-        // (a) src1 is a held-back RMS_NORM * w (graph_compute): when the group holds every reader of it the kernels form the normed
-        //     row themselves; otherwise it is materialized now, as the graph says
-        if (ctx->pending_norm.mul == b) {
-            const auto pn = ctx->pending_norm;
-            ctx->pending_norm = {};
-            // the kernels read the un-normed row while they write their results: a result that ggml-alloc placed in the block of
-            // that row (dead once the norm has run, in the graph's order) would be overwritten under the staging of other workgroups
-            bool norm_in_kernel = n == pn.readers && folds;
-            for (int i = 0; norm_in_kernel && i < n; ++i)
-                norm_in_kernel = !bytes_overlap(ws[i].dst, (size_t) ((N - 1) * ws[i].ldd + ws[i].M) * sizeof(float), to_qt(pn.rn->src[0], ctx).data, ggml_nbytes(pn.rn->src[0]));
-            if (pn.add) {
-                // a prompt batch (site_add_rms_norm held ADD -> RMS_NORM -> MUL back): the group's activation prep adds, norms and stores the
-                // sum.  The products are written by later launches of the same stream, so they may sit on the dead operands; not on the sum
-                const ggml_tensor * x0 = pn.add->src[0], * x1 = pn.add->src[1];
-                norm_in_kernel = n == pn.readers && folds && qmm_mul_mat_group_norm_supported(q, ws, n, K, N);
-                for (int i = 0; norm_in_kernel && i < n; ++i)
-                    norm_in_kernel = !bytes_overlap(ws[i].dst, (size_t) ((N - 1) * ws[i].ldd + ws[i].M) * sizeof(float), to_qt(pn.add, ctx).data, ggml_nbytes(pn.add));
-                if (norm_in_kernel) {
-                    x = (const float *) to_qt(x0, ctx).data;
-                    ldx = x0->nb[1] / sizeof(float);
-                    ex.norm_w = (const float *) pn.w->data;
-                    memcpy(&ex.norm_eps, pn.rn->op_params, sizeof(float));
-                    ex.norm_add = (const float *) to_qt(x1, ctx).data;
-                    ex.norm_add_ld = x1->nb[1] / sizeof(float);
-                    ex.norm_sum = (float *) to_qt(pn.add, ctx).data;
-                    ex.norm_sum_ld = pn.add->nb[1] / sizeof(float);
-                    use_ex = true;
-                    if (dbg()) fprintf(stderr, "fused: add + norm (%s) into the prep of %s\n", pn.add->name, dst->name);
-                } else {                                                              // the graph's three nodes after all, as the site would have run them
-                    // TODO(advisor r3): the site's own launch asks early_write_ok of `mul` against the ADD's operands (e_ok); neither the
-                    // hold-back test nor this path does
-                    const qmm_tensor a = to_qt(x0, ctx), bb = to_qt(x1, ctx), w = to_qt(pn.w, ctx), sum = to_qt(pn.add, ctx), d = to_qt(pn.mul, ctx);
-                    float eps;
-                    memcpy(&eps, pn.rn->op_params, sizeof(float));
-                    if (dbg()) fprintf(stderr, "fusion declined: add + norm (%s) into the prep of %s (group of %d of %d readers)\n", pn.add->name, dst->name, n, pn.readers);
-                    if (qmm_op_add_rms_norm(q, &a, &bb, &w, &sum, &d, eps, st)) {
-                        GGML_LOG_ERROR("MI355X ADD+RMS_NORM(%s): %s\n", pn.add->name, qmm_last_error());
-                        return GGML_STATUS_FAILED;
-                    }
-                }
-            } else if (norm_in_kernel) {
-                const qmm_tensor qx = to_qt(pn.rn->src[0], ctx);
-                x = (const float *) qx.data;
-                ldx = pn.rn->src[0]->nb[1] / sizeof(float);
-                ex.norm_w = (const float *) pn.w->data;
-                memcpy(&ex.norm_eps, pn.rn->op_params, sizeof(float));
-                use_ex = true;
-            } else {
-                ggml_tensor tmp = *pn.mul;
-                memcpy(tmp.op_params, pn.rn->op_params, sizeof(tmp.op_params));
-                const enum ggml_status s = compute_glue(ctx, &tmp, QMM_OP_RMS_NORM_MUL, pn.rn->src[0], pn.w, nullptr);
-                if (s != GGML_STATUS_SUCCESS) return s;
-            }
-        }
-        // (c) ffn_gate + ffn_up of a few-token batch whose only readers are silu(gate) and the MUL of the two (build_ffn's SwiGLU):
-        //     the kernel pairs the rows and writes the product; neither projection is stored
-        if (n == 2 && folds && N <= QMM_MATVEC_MAX_N && qmm::mv_swiglu_pair(ws[0].type, ws[0].M, ws[1].type, ws[1].M) && !fuse_off()) {
-            auto uses = [&](const ggml_tensor * t) {
-                auto it = std::lower_bound(ctx->readers.begin(), ctx->readers.end(), t,
-                                           [](const mi355x_backend_ctx::reader_info & r, const ggml_tensor * y) { return r.t < y; });
-                return it != ctx->readers.end() && it->t == t ? it->uses : -1;
-            };
-            const ggml_tensor * t0 = nodes[0], * t1 = nodes[member[1]];
-            int js = -1, jm = -1;
-            for (int j = 1; j < n_nodes && j <= 2 * LOOKAHEAD && jm < 0; ++j) {
-                const ggml_tensor * t = nodes[j];
-                if (done[j] || is_noop(t)) continue;
-                if (js < 0) {
-                    if (t->op == GGML_OP_UNARY && ggml_get_unary_op(t) == GGML_UNARY_OP_SILU && (t->src[0] == t0 || t->src[0] == t1)) js = j;
-                    else break;
-                } else {
-                    const ggml_tensor * other = nodes[js]->src[0] == t0 ? t1 : t0;
-                    if (t->op == GGML_OP_MUL && ((t->src[0] == nodes[js] && t->src[1] == other) || (t->src[1] == nodes[js] && t->src[0] == other))) jm = j;
-                    else break;
-                }
-            }
-            // the product lands in the MUL's buffer while the launch still stages x: that buffer must be disjoint from x and from
-            // everything the nodes in between (run later) still read or write
-            bool early_ok = jm >= 0 && !bytes_overlap(nodes[jm]->data, ggml_nbytes(nodes[jm]), x, (size_t) ((N - 1) * ldx + K) * sizeof(float));
-            for (int j = 1; early_ok && j < jm; ++j) {
-                if (done[j] || is_noop(nodes[j]) || j == js) continue;
-                early_ok = !ranges_overlap(nodes[jm], nodes[j]);
-                for (int k = 0; early_ok && k < GGML_MAX_SRC && nodes[j]->src[k]; ++k) early_ok = !ranges_overlap(nodes[jm], nodes[j]->src[k]);
-            }
-            if (jm >= 0 && !early_ok && dbg()) fprintf(stderr, "fusion declined: SwiGLU into %s\n", nodes[jm]->name);
-            if (jm >= 0 && early_ok && uses(t0) == 1 && uses(t1) == 1 && uses(nodes[js]) == 1 && ggml_are_same_shape(nodes[jm], t0) && nodes[jm]->nb[0] == 4 &&
-                !(nodes[jm]->flags & GGML_TENSOR_FLAG_OUTPUT) && !(t0->flags & GGML_TENSOR_FLAG_OUTPUT) && !(t1->flags & GGML_TENSOR_FLAG_OUTPUT) &&
-                qmm::mv_fits_swiglu(N, K, ex.norm_w != nullptr)) {
-                ex.swiglu = nodes[js]->src[0] == t0 ? 1 : 2;
-                ws[0].dst = (float *) nodes[jm]->data;
-                ws[0].ldd = (int64_t) (nodes[jm]->nb[1] / sizeof(float));
-                done[js] = done[jm] = 1;
-                use_ex = true;
-            }
-        }
-        // (b) a lone MUL_MAT whose only reader is the residual ADD right behind it (wo, ffn_down): dst = W x + residual, written
-        //     where the ADD would have put it
-        if (n == 1 && folds && N <= QMM_MATVEC_MAX_N && !fuse_off() && !(dst->flags & GGML_TENSOR_FLAG_OUTPUT)) {
-            int j = 1;
-            while (j < n_nodes && (done[j] || is_noop(nodes[j]))) ++j;
-            const ggml_tensor * add = j < n_nodes ? nodes[j] : nullptr;
-            auto it = std::lower_bound(ctx->readers.begin(), ctx->readers.end(), dst,
-                                       [](const mi355x_backend_ctx::reader_info & r, const ggml_tensor * t) { return r.t < t; });
-            const bool single = it != ctx->readers.end() && it->t == dst && it->uses == 1;
-            if (add && single && add->op == GGML_OP_ADD && (add->src[0] == dst || add->src[1] == dst) && add->src[0] != add->src[1]) {
-                const ggml_tensor * r = add->src[0] == dst ? add->src[1] : add->src[0];
-                // dst = W x + r is written where the ADD would put it, while x is still being staged by other workgroups: the ADD's buffer must
-                // not be x's (ggml-alloc may hand the ADD the block of the dead src1), and r only where it is the very same rows (in place)
-                const qmm_tensor qr = to_qt(r, ctx);
-                const bool r_ok = !bytes_overlap(add->data, ggml_nbytes(add), qr.data, ggml_nbytes(r)) || (qr.data == add->data && r->nb[1] == add->nb[1]);
-                const bool x_ok = !bytes_overlap(add->data, ggml_nbytes(add), x, (size_t) ((N - 1) * ldx + K) * sizeof(float));
-                if ((!r_ok || !x_ok) && dbg()) fprintf(stderr, "fusion declined: residual into %s\n", add->name);
-                if (r_ok && x_ok && ggml_are_same_shape(r, dst) && ggml_are_same_shape(add, dst) && r->type == GGML_TYPE_F32 && r->nb[0] == 4 && add->nb[0] == 4 &&
-                    r->nb[1] == add->nb[1] && add->nb[1] % 4 == 0) {
-                    ex.residual[0] = (const float *) to_qt(r, ctx).data;
-                    ws[0].dst = (float *) add->data;
-                    ws[0].ldd = (int64_t) (add->nb[1] / sizeof(float));
-                    done[j] = 1;
-                    use_ex = true;
-                }
-            }
-        }
-        if (use_ex ? qmm_mul_mat_group_ex(q, ws, n, K, x, N, ldx, &ex, st) : qmm_mul_mat_group(q, ws, n, K, x, N, ldx, st)) {
-            GGML_LOG_ERROR("MI355X MUL_MAT(%s): %s\n", dst->name, qmm_last_error());
-            return GGML_STATUS_FAILED;
-        }
-        return GGML_STATUS_SUCCESS;
-    }
-    // batched / broadcast form: one 2-D product per (i12, i13), src0 broadcast as ggml_compute_forward_mul_mat does
-    // (ggml-cpu.c:6711-6716: i03 = i13 / r3, i02 = i12 / r2)
-    const int64_t r2 = b->ne[2] / a->ne[2], r3 = b->ne[3] / a->ne[3];
-    for (int64_t i13 = 0; i13 < b->ne[3]; ++i13)
-        for (int64_t i12 = 0; i12 < b->ne[2]; ++i12) {
-            const char * wp = (const char *) a->data + (i12 / r2) * a->nb[2] + (i13 / r3) * a->nb[3];
-            const char * xp = (const char *) b->data + i12 * b->nb[2] + i13 * b->nb[3];
-            char * dp = (char *) dst->data + i12 * dst->nb[2] + i13 * dst->nb[3];
-            if (qmm_mul_mat(q, weight_type(ctx, a), wp, a->nb[1], K, a->ne[1], (const float *) xp, N, b->nb[1] / sizeof(float),
-                            (float *) dp, dst->nb[1] / sizeof(float), st)) {
-                GGML_LOG_ERROR("MI355X MUL_MAT(%s): %s\n", dst->name, qmm_last_error());
-                return GGML_STATUS_FAILED;
-            }
-        }
-    return GGML_STATUS_SUCCESS;
-}
-
-// ffn_gate_exps and ffn_up_exps are consecutive MUL_MAT_ID nodes on the same src1 and ids (llama.cpp build_moe_ffn): when the
-// next node is such a twin, both go out in one call (one mat-vec launch, or one expert sort + activation prep)
-bool moe_twin(const ggml_tensor * d0, const ggml_tensor * d1) {
-    if (d1->op != GGML_OP_MUL_MAT_ID || !supports_mul_mat_id(d1)) return false;
-    const ggml_tensor * a0 = d0->src[0], * a1 = d1->src[0];
-    if (d0->src[1] != d1->src[1] || d0->src[2] != d1->src[2] || a0 == a1 || !is_ours(a1) || !is_ours(d1)) return false;
-    if (a0->type != a1->type || !ggml_are_same_shape(a0, a1) || a0->nb[1] != a1->nb[1] || a0->nb[2] != a1->nb[2]) return false;
-    return d0->nb[1] == d1->nb[1] && d0->nb[2] == d1->nb[2] && ggml_are_same_shape(d0, d1);
-}
-
-enum ggml_status compute_mul_mat_id(mi355x_backend_ctx * ctx, ggml_tensor * const * nodes, int n_nodes, char * done) {
-    const ggml_tensor * dst = nodes[0];
-    const ggml_tensor * as = dst->src[0], * b = dst->src[1], * ids = dst->src[2];
-    qmm_ctx * q = ctx->dev->qmm;
-    // the twin (ffn_up_exps after ffn_gate_exps) may sit behind the SILU of the first one
-    int twin = 0;
-    std::vector<const ggml_tensor *> & skipped = ctx->skipped;
-    skipped.clear();
-    for (int i = 1; i < n_nodes && i <= LOOKAHEAD && !twin && !fuse_off(); ++i) {
-        if (done[i] || is_noop(nodes[i])) continue;
-        if (moe_twin(dst, nodes[i]) && can_hoist(nodes[i], skipped)) twin = i;
-        else skipped.push_back(nodes[i]);
-        if (nodes[i]->op == GGML_OP_MUL_MAT_ID && !twin) break;
-    }
-    if (twin) {
-        const ggml_tensor * dst1 = nodes[twin];
-        const int t0 = weight_type(ctx, as), t1 = weight_type(ctx, dst1->src[0]);
-        if (t0 != t1) { GGML_LOG_ERROR("MI355X MUL_MAT_ID pair: layouts differ\n"); return GGML_STATUS_FAILED; }
-        // Token generation: the SwiGLU behind the pair (ggml_silu of one, ggml_mul with the other: ffn_moe_gate_par) in the same launch
-        // (round 3).  gate, up and the silu are then never written: each must have exactly the one reader of the pattern, all of them
-        // provably in this split (analyze_readers); the product is written HERE, two or three nodes early, while other workgroups still
-        // stage src1 and read the ids, and across whatever else the graph lists in between.
-        if (qmm_mul_mat_id_swiglu_supported(ids->ne[0], ids->ne[1]) && !sw().moe_swiglu_off) {
-            auto uses = [&](const ggml_tensor * t) {
-                const auto & rd = ctx->readers;
-                auto it = std::lower_bound(rd.begin(), rd.end(), t, [](const mi355x_backend_ctx::reader_info & x, const ggml_tensor * y) { return x.t < y; });
-                return it != rd.end() && it->t == t ? it->uses : 1 << 20;
-            };
-            int i_silu = 0, i_mul = 0;
-            std::vector<const ggml_tensor *> between;
-            for (int i = 1; i < n_nodes && i <= 2 * LOOKAHEAD && !i_mul; ++i) {
-                const ggml_tensor * t = nodes[i];
-                if (i == twin || done[i] || is_noop(t)) continue;
-                if (!i_silu && t->op == GGML_OP_UNARY && ggml_get_unary_op(t) == GGML_UNARY_OP_SILU && (t->src[0] == dst || t->src[0] == dst1)) { i_silu = i; continue; }
-                if (i_silu && t->op == GGML_OP_MUL) {
-                    const ggml_tensor * sl = nodes[i_silu], * other = sl->src[0] == dst ? dst1 : dst;
-                    if ((t->src[0] == sl && t->src[1] == other) || (t->src[1] == sl && t->src[0] == other)) { i_mul = i; continue; }
-                }
-                between.push_back(t);
-            }
-            if (i_silu && i_mul) {
-                const ggml_tensor * sl = nodes[i_silu], * par = nodes[i_mul];
-                const ggml_tensor * gate = sl->src[0], * up = gate == dst ? dst1 : dst;
-                const bool flags_ok = !((gate->flags | up->flags | sl->flags) & GGML_TENSOR_FLAG_OUTPUT);
-                if (flags_ok && uses(gate) == 1 && uses(up) == 1 && uses(sl) == 1 && is_ours(par) && par->type == GGML_TYPE_F32 && ggml_are_same_shape(par, dst) &&
-                    par->nb[0] == 4 && par->nb[1] == dst->nb[1] && par->nb[2] == dst->nb[2] && can_hoist(par, between) && early_write_ok(par, { b, ids })) {
-                    if (qmm_mul_mat_id_swiglu(q, t0, gate->src[0]->data, up->src[0]->data, as->nb[1], as->nb[2], as->ne[0], as->ne[1], as->ne[2],
-                                              (const float *) b->data, b->ne[1], b->nb[1], b->nb[2],
-                                              (const int32_t *) ids->data, ids->ne[0], ids->ne[1], ids->nb[1],
-                                              (float *) par->data, par->nb[1], par->nb[2], qmm_stream(q))) {
-                        GGML_LOG_ERROR("MI355X MUL_MAT_ID + SwiGLU(%s, %s): %s\n", dst->name, dst1->name, qmm_last_error());
-                        return GGML_STATUS_FAILED;
-                    }
-                    if (dbg()) fprintf(stderr, "fused: expert pair + swiglu (%s)\n", par->name);
-                    done[twin] = 1; done[i_silu] = 1; done[i_mul] = 1;
-                    return GGML_STATUS_SUCCESS;
-                }
-            }
-        }
-        if (qmm_mul_mat_id_pair(q, t0, as->data, dst1->src[0]->data, as->nb[1], as->nb[2], as->ne[0], as->ne[1], as->ne[2],
-                                (const float *) b->data, b->ne[1], b->nb[1], b->nb[2],
-                                (const int32_t *) ids->data, ids->ne[0], ids->ne[1], ids->nb[1],
-                                (float *) dst->data, (float *) dst1->data, dst->nb[1], dst->nb[2], qmm_stream(q))) {
-            GGML_LOG_ERROR("MI355X MUL_MAT_ID(%s, %s): %s\n", dst->name, dst1->name, qmm_last_error());
-            return GGML_STATUS_FAILED;
-        }
-        done[twin] = 1;
-        return GGML_STATUS_SUCCESS;
-    }
-    if (qmm_mul_mat_id(q, weight_type(ctx, as), as->data, as->nb[1], as->nb[2], as->ne[0], as->ne[1], as->ne[2],
-                       (const float *) b->data, b->ne[1], b->nb[1], b->nb[2],
-                       (const int32_t *) ids->data, ids->ne[0], ids->ne[1], ids->nb[1],
-                       (float *) dst->data, dst->nb[1], dst->nb[2], qmm_stream(q))) {
-        GGML_LOG_ERROR("MI355X MUL_MAT_ID(%s): %s\n", dst->name, qmm_last_error());
-        return GGML_STATUS_FAILED;
-    }
-    return GGML_STATUS_SUCCESS;
-}
-
 // the analysis step of a graph_compute call
 void analyze_readers(mi355x_backend_ctx * ctx, const ggml_cgraph * cgraph) {
     // Reader analysis.  Candidates are the nodes a fusion wants to skip or move: RMS_NORM / SILU (fused into the MUL behind them),
@@ -493,7 +205,6 @@ void analyze_readers(mi355x_backend_ctx * ctx, const ggml_cgraph * cgraph) {
     std::vector<mi355x_backend_ctx::reader_info> & rd = ctx->readers;
     ctx->redirects.clear();
     ctx->hoist_used = 0;
-    ctx->pending_norm = {};
     // Token generation hands over the same graph again and again (same tensors at the same addresses: llama.cpp rebuilds it in the same
     // context memory, ggml-alloc places it the same way; only offsets INTO the KV cache move, and the cache is nobody's candidate): the
     // analysis below depends on nothing but what this signature covers, so an unchanged signature keeps the previous result
@@ -526,7 +237,7 @@ void analyze_readers(mi355x_backend_ctx * ctx, const ggml_cgraph * cgraph) {
                 const ggml_tensor * n = cgraph->nodes[i];
                 if (is_noop(n)) continue;                                          // a view reads nothing; its readers are found through view_src
                 const bool glue = glue_op(n) != 0 || n->op == GGML_OP_FLASH_ATTN_EXT;     // (compute_flash_attn resolves its four operands through to_qt as well)
-                // a quantized 2-D MUL_MAT of this device takes its src1 pointer through to_qt as well (compute_mul_mat)
+                // a quantized 2-D MUL_MAT of this device takes its src1 pointer through to_qt as well (form_group)
                 const bool mm_src1 = !glue && n->op == GGML_OP_MUL_MAT && n->src[0] && n->src[1] && !is_split(n->src[0]) && n->src[0]->ne[2] == 1 &&
                                      n->src[0]->ne[3] == 1 && n->src[1]->ne[2] == 1 && n->src[1]->ne[3] == 1;
                 for (int j = 0; j < GGML_MAX_SRC && n->src[j]; ++j) {
@@ -573,54 +284,24 @@ void analyze_readers(mi355x_backend_ctx * ctx, const ggml_cgraph * cgraph) {
     }
 }
 
-// ---- one graph_compute call (analysis / plan / issue apart) -----------------------------------------------------------
-// analyze_readers() is the analysis; graph_pass holds what the launch sites share.  Every site_* looks at node i and returns 1 when it
-// issued (or deferred) the node, possibly together with later nodes that it marks in done[]; 0 when its pattern is not there (the
-// caller tries the next site, in the order below, and finally the node's own launch); -1 when a launch failed.
-struct graph_pass {
-    mi355x_backend_ctx * ctx;
-    ggml_cgraph * cgraph;
-    int n_nodes;
-    std::vector<char> & done;
-    std::vector<const ggml_tensor *> & deferred;
-    const mi355x_backend_ctx::reader_info * info(const ggml_tensor * t) const {
-        const auto & rd = ctx->readers;
-        auto it = std::lower_bound(rd.begin(), rd.end(), t, [](const mi355x_backend_ctx::reader_info & x, const ggml_tensor * y) { return x.t < y; });
-        return it != rd.end() && it->t == t ? &*it : nullptr;
+// The quantized MUL_MATs that read `b` (group_member), looked for among the live nodes from `start` on: n of them, the first `cap` at
+// at[]; `all` when they are every reader `b` has in this graph, at least one and at most `cap`.  The scan ends at the first live
+// node in front of them that is something else (it reads or runs first: the graph's order stays).  Both hold-back sites pass
+// cap = 4, the size of a group (site_add_rms_norm used to stop counting there, the few-token site counted on and compared
+// afterwards: the same answer, since every member is a reader).
+graph_pass::reader_group graph_pass::scan_reader_group(const ggml_tensor * b, int start, int cap) const {
+    reader_group g;
+    const auto * ri = info(b);
+    for (int j = start; j < n_nodes && j <= start + LOOKAHEAD && ri && g.n < cap; ++j) {
+        const ggml_tensor * t = cgraph->nodes[j];
+        if (done[j] || is_noop(t)) continue;
+        if (group_member(t, b, false)) g.at[g.n++] = j;
+        else if (g.n == 0) break;                                          // something else reads or runs first: keep the graph's order
     }
-    bool single_use(const ggml_tensor * t) const {
-        const auto * r = info(t);
-        return r && r->uses == 1;
-    }
-    // The quantized MUL_MATs that read `b` (group_member), looked for among the live nodes from `start` on: n of them, the first `cap` at
-    // at[]; `all` when they are every reader `b` has in this graph, at least one and at most `cap`.  The scan ends at the first live
-    // node in front of them that is something else (it reads or runs first: the graph's order stays).  Both hold-back sites pass
-    // cap = 4, the size of a group (site_add_rms_norm used to stop counting there, the few-token site counted on and compared
-    // afterwards: the same answer, since every member is a reader).
-    struct reader_group { int n = 0; int at[4] = { 0, 0, 0, 0 }; bool all = false; };
-    reader_group scan_reader_group(const ggml_tensor * b, int start, int cap) const {
-        reader_group g;
-        const auto * ri = info(b);
-        for (int j = start; j < n_nodes && j <= start + LOOKAHEAD && ri && g.n < cap; ++j) {
-            const ggml_tensor * t = cgraph->nodes[j];
-            if (done[j] || is_noop(t)) continue;
-            if (group_member(t, b, false)) g.at[g.n++] = j;
-            else if (g.n == 0) break;                                          // something else reads or runs first: keep the graph's order
-        }
-        g.all = ri && g.n >= 1 && g.n == ri->uses;
-        for (int m = 0; m < g.n; ++m) g.all = g.all && !bf16_weight(cgraph->nodes[g.at[m]]->src[0]);      // no norm is held back for a BF16 group
-        return g;
-    }
-    int site_deferred_silu_mul(int i, ggml_tensor * node, int gop);
-    int site_hold_silu(int i, ggml_tensor * node, int gop);
-    int site_add_rms_norm(int i, ggml_tensor * node, int gop);
-    int site_rms_norm_mul(int i, ggml_tensor * node, int gop);
-    int site_attention(int i, ggml_tensor * node, int gop);
-    int site_kqv_into_merged_heads(int i, ggml_tensor * node, int gop);
-    int site_moe_combine(int i, ggml_tensor * node, int gop);
-    int site_moe_router(int i, ggml_tensor * node, int gop);
-    int site_rope_kv_attention(int i, ggml_tensor * node, int gop);
-};
+    g.all = ri && g.n >= 1 && g.n == ri->uses;
+    for (int m = 0; m < g.n; ++m) g.all = g.all && !bf16_weight(cgraph->nodes[g.at[m]]->src[0]);      // no norm is held back for a BF16 group
+    return g;
+}
 
 // a MUL whose operand is a SILU that was held back (site_hold_silu): silu(gate) * up in one pass, or folded into the staging of the MUL_MAT behind it
 int graph_pass::site_deferred_silu_mul(int i, ggml_tensor * node, int gop) {
@@ -632,15 +313,14 @@ int graph_pass::site_deferred_silu_mul(int i, ggml_tensor * node, int gop) {
         const ggml_tensor * gate = silu->src[0], * up = node->src[0] == silu ? node->src[1] : node->src[0];
         // prompt batch, and the product feeds exactly one quantized MUL_MAT right behind it (ffn_down): that MUL_MAT's
         // activation prep reads gate and up itself; no launch and no round trip for the product
-        int j = i + 1;
-        while (j < n_nodes && (done[j] || is_noop(cgraph->nodes[j]))) ++j;
+        const int j = next_live(i + 1);
         if (j < n_nodes && node->ne[1] > QMM_MATVEC_MAX_N && node->ne[2] == 1 && node->ne[3] == 1 && single_use(node) &&
             !(node->flags & GGML_TENSOR_FLAG_OUTPUT) && !sw().prec_set) {
             const ggml_tensor * mm = cgraph->nodes[j];
             const qmm_tensor qg = to_qt(gate, ctx), qu = to_qt(up, ctx);      // resolved now: a redirect may expire before node j
             if (group_member(mm, node, false) && !bf16_weight(mm->src[0]) && gate->nb[0] == 4 && up->nb[0] == 4 && gate->nb[1] % 16 == 0 && up->nb[1] % 16 == 0 &&
                 (uintptr_t) qg.data % 16 == 0 && (uintptr_t) qu.data % 16 == 0) {
-                ctx->swiglu_in[j] = { (const float *) qg.data, (const float *) qu.data, (int64_t) (gate->nb[1] / 4), (int64_t) (up->nb[1] / 4) };
+                pending_swiglu = { (const float *) qg.data, (const float *) qu.data, (int64_t) (gate->nb[1] / 4), (int64_t) (up->nb[1] / 4), mm };
                 return 1;
             }
         }
@@ -683,7 +363,7 @@ int graph_pass::site_add_rms_norm(int i, ggml_tensor * node, int gop) {
         if (rn->op == GGML_OP_RMS_NORM && rn->src[0] == node && single_use(rn) && fused_pair(rn, mul, &other) == QMM_OP_RMS_NORM_MUL) {
             const qmm_tensor a = to_qt(node->src[0], ctx), b = to_qt(node->src[1], ctx), w = to_qt(other, ctx), sum = to_qt(node, ctx), d = to_qt(mul, ctx);
             // A prompt batch whose normed rows are read by ONE group of quantized MUL_MATs right behind the MUL (q / k / v, gate / up) and by
-            // nothing else: no launch here; the group's activation prep adds, norms and stores the sum (compute_mul_mat; round 3)
+            // nothing else: no launch here; the group's activation prep adds, norms and stores the sum (fold_norm; round 3)
             if (node->ne[1] > QMM_MATVEC_MAX_N && node->ne[2] == 1 && node->ne[3] == 1 && ggml_are_same_shape(node->src[0], node->src[1]) &&
                 ggml_are_same_shape(node, node->src[0]) && !sw().prep_norm_off) {
                 const reader_group g = scan_reader_group(mul, i + 3, 4);
@@ -701,7 +381,7 @@ int graph_pass::site_add_rms_norm(int i, ggml_tensor * node, int gop) {
                     // the sum is stored while other rows of the operands are still read: in place over an operand only with the same rows
                     early_write_ok(node, { x0 }, x0) && early_write_ok(node, { x1 }, x1) && early_write_ok(node, { other }) &&
                     qmm_mul_mat_group_norm_supported(ctx->dev->qmm, gw, found, node->ne[0], node->ne[1])) {
-                    ctx->pending_norm = { rn, mul, other, found, node };
+                    pending_norm = { rn, mul, other, found, node };
                     done[i + 1] = done[i + 2] = 1;
                     if (dbg()) fprintf(stderr, "held back: add + norm (%s, %s) for the prep of %d MUL_MATs\n", node->name, mul->name, found);
                     return 1;
@@ -713,9 +393,7 @@ int graph_pass::site_add_rms_norm(int i, ggml_tensor * node, int gop) {
                               (early_write_ok(mul, { node->src[1], other, node }, nullptr) && early_write_ok(mul, { node->src[0] }, node->src[0])) ||
                               (early_write_ok(mul, { node->src[0], other, node }, nullptr) && early_write_ok(mul, { node->src[1] }, node->src[1]));
             if (e_ok && qmm_op_add_rms_norm_supported(&a, &b, &w, &sum, &d)) {
-                float eps;
-                memcpy(&eps, rn->op_params, sizeof(float));
-                if (qmm_op_add_rms_norm(ctx->dev->qmm, &a, &b, &w, &sum, &d, eps, qmm_stream(ctx->dev->qmm))) {
+                if (qmm_op_add_rms_norm(ctx->dev->qmm, &a, &b, &w, &sum, &d, rms_eps(rn), qmm_stream(ctx->dev->qmm))) {
                     GGML_LOG_ERROR("MI355X ADD+RMS_NORM(%s): %s\n", node->name, qmm_last_error());
                     return -1;
                 }
@@ -838,8 +516,7 @@ int graph_pass::site_moe_combine(int i, ggml_tensor * node, int gop) {
             // while other workgroups (one per token) still read the expert rows, the weights and the residual: l_out and the normed row
             // must be clear of the experts and the weights (another layout) and may sit on the residual only as the very same rows.
             const ggml_tensor * last = cgraph->nodes[idx[U - 2]];
-            int ja = idx[U - 2] + 1;
-            while (ja < n_nodes && (done[ja] || is_noop(cgraph->nodes[ja]))) ++ja;
+            const int ja = next_live(idx[U - 2] + 1);
             const ggml_tensor * other = nullptr;
             if (ja + 2 < n_nodes && single_use(last) && !(last->flags & GGML_TENSOR_FLAG_OUTPUT)) {
                 ggml_tensor * add = cgraph->nodes[ja], * rn = cgraph->nodes[ja + 1], * mul = cgraph->nodes[ja + 2];
@@ -856,9 +533,7 @@ int graph_pass::site_moe_combine(int i, ggml_tensor * node, int gop) {
                         const qmm_tensor x = to_qt(node->src[0], ctx), w = to_qt(node->src[1], ctx), qb = to_qt(r, ctx), nw = to_qt(other, ctx), qs = to_qt(add, ctx),
                                          qd = to_qt(mul, ctx);
                         if (qmm_moe_combine_add_rms_norm_supported(&x, &w, &qb, &nw, &qs, &qd)) {
-                            float eps;
-                            memcpy(&eps, rn->op_params, sizeof(float));
-                            if (qmm_moe_combine_add_rms_norm(ctx->dev->qmm, &x, &w, &qb, &nw, &qs, &qd, eps, qmm_stream(ctx->dev->qmm))) {
+                            if (qmm_moe_combine_add_rms_norm(ctx->dev->qmm, &x, &w, &qb, &nw, &qs, &qd, rms_eps(rn), qmm_stream(ctx->dev->qmm))) {
                                 GGML_LOG_ERROR("MI355X MoE combine + ADD + RMS_NORM(%s): %s\n", node->name, qmm_last_error());
                                 return -1;
                             }
@@ -908,8 +583,7 @@ int graph_pass::site_moe_router(int i, ggml_tensor * node, int gop) {
     if (node->op == GGML_OP_RMS_NORM && i + 2 < n_nodes && node->ne[1] <= 8 && node->ne[2] == 1 && node->ne[3] == 1 && single_use(node) && !fuse_off() &&
         !sw().router_norm_off && !sw().router_logits_off) {
         ggml_tensor * m = cgraph->nodes[i + 1];
-        int j2 = i + 2;                                                         // (the 3-D reshape of the normed row for the expert MUL_MAT_IDs sits in between)
-        while (j2 < n_nodes && (done[j2] || is_noop(cgraph->nodes[j2]))) ++j2;
+        const int j2 = next_live(i + 2);                                        // (the 3-D reshape of the normed row for the expert MUL_MAT_IDs sits in between)
         if (j2 >= n_nodes || done[i + 1] || fused_pair(node, m, &nwgt) != QMM_OP_RMS_NORM_MUL) return 0;
         ggml_tensor * t = cgraph->nodes[j2];
         if (t->op != GGML_OP_MUL_MAT || t->src[1] != m || t->src[0]->type != GGML_TYPE_F32 || (m->flags & GGML_TENSOR_FLAG_OUTPUT)) return 0;
@@ -919,8 +593,7 @@ int graph_pass::site_moe_router(int i, ggml_tensor * node, int gop) {
     }
     if (node->op == GGML_OP_MUL_MAT && node->src[0]->type == GGML_TYPE_F32 && node->src[1]->type == GGML_TYPE_F32 && node->type == GGML_TYPE_F32 && node->ne[0] <= 64 &&
         node->ne[1] <= 8 && node->ne[2] == 1 && node->ne[3] == 1 && !fuse_off() && !sw().router_logits_off) {
-        int j = i + 1;
-        while (j < n_nodes && (done[j] || is_noop(cgraph->nodes[j]))) ++j;
+        const int j = next_live(i + 1);
         if (j >= n_nodes || cgraph->nodes[j]->op != GGML_OP_SOFT_MAX || cgraph->nodes[j]->src[0] != node) return 0;
         lgt = node;
         i = j;
@@ -978,13 +651,11 @@ int graph_pass::site_moe_router(int i, ggml_tensor * node, int gop) {
                     if (!early_write_ok(lgt, { x0, nwgt, nmul, lgt->src[0] }) || !early_write_ok(as, { x0, nwgt, nmul }) ||
                         (to_qt(dv, ctx).data == dv->data && !early_write_ok(dv, { x0, nwgt, nmul }))) return 0;
                     const qmm_tensor gi = to_qt(lgt->src[0], ctx), xin = to_qt(x0, ctx), nw = to_qt(nwgt, ctx), ny = to_qt(nmul, ctx);
-                    float eps;
-                    memcpy(&eps, nrm->op_params, sizeof(float));
                     if (!is_ours(lgt->src[0]) || is_split(lgt->src[0]) || !qmm_moe_router_logits_norm_supported(&gi, &xin, &nw, &ny, &lg, &ids, &w, n_used)) {
                         if (dbg()) fprintf(stderr, "fusion declined: moe router with its norm (%s): operands not supported\n", nmul->name);
                         return 0;
                     }
-                    if (qmm_moe_router_logits_norm(ctx->dev->qmm, &gi, &xin, &nw, eps, &ny, &lg, &ids, &w, n_used, 1, qmm_stream(ctx->dev->qmm))) {
+                    if (qmm_moe_router_logits_norm(ctx->dev->qmm, &gi, &xin, &nw, rms_eps(nrm), &ny, &lg, &ids, &w, n_used, 1, qmm_stream(ctx->dev->qmm))) {
                         GGML_LOG_ERROR("MI355X MoE router with norm and logits(%s): %s\n", node->name, qmm_last_error());
                         return -1;
                     }
@@ -1130,7 +801,7 @@ int graph_pass::site_rope_kv_attention(int i, ggml_tensor * node, int gop) {
 }
 
 // RMS_NORM -> MUL(w) (build_norm).  Few tokens, and every reader of the normed row a quantized MUL_MAT of one group (q / k / v, gate / up,
-// output): no launch here, compute_mul_mat hands the norm to the mat-vec kernels, or materializes it if the group turns out smaller.
+// output): no launch here, fold_norm hands the norm to the mat-vec kernels, or materializes it if the group turns out smaller.
 // Otherwise the pair as one launch.  (One site for both, so that the pair is probed once.)
 int graph_pass::site_rms_norm_mul(int i, ggml_tensor * node, int gop) {
     (void) gop;
@@ -1145,7 +816,7 @@ int graph_pass::site_rms_norm_mul(int i, ggml_tensor * node, int gop) {
         if (g.all && !(mul->flags & GGML_TENSOR_FLAG_OUTPUT) && x->nb[0] == 4 && x->nb[1] % 16 == 0 &&
             (uintptr_t) to_qt(x, ctx).data % 16 == 0 && (uintptr_t) other->data % 16 == 0 && K % 256 == 0 &&
             qmm::mv_fits_norm(N, K)) {
-            ctx->pending_norm = { node, mul, other, g.n };
+            pending_norm = { node, mul, other, g.n };
             done[i + 1] = 1;
             return 1;
         }
@@ -1182,7 +853,6 @@ enum ggml_status graph_compute_once(ggml_backend_t backend, struct ggml_cgraph *
     done.assign(n_nodes, 0);
     std::vector<const ggml_tensor *> & deferred = ctx->deferred;
     deferred.assign(n_nodes, nullptr);
-    ctx->swiglu_in.assign(n_nodes, {});
     graph_pass P{ ctx, cgraph, n_nodes, done, deferred };
     for (int i = 0; i < n_nodes; ++i) {
         struct ggml_tensor * node = cgraph->nodes[i];
@@ -1209,19 +879,10 @@ enum ggml_status graph_compute_once(ggml_backend_t backend, struct ggml_cgraph *
             } else {
                 st = compute_glue(ctx, node, gop, node->src[0], node->src[1], node->src[2]);
             }
-        } else if (node->op == GGML_OP_MUL_MAT && ctx->swiglu_in[i].gate) {
-            const ggml_tensor * w = node->src[0];
-            const auto & sg = ctx->swiglu_in[i];
-            st = GGML_STATUS_SUCCESS;
-            if (qmm_mul_mat_swiglu_in(ctx->dev->qmm, weight_type(ctx, w), w->data, w->nb[1], w->ne[0], w->ne[1], sg.gate, sg.ld_gate, sg.up, sg.ld_up,
-                                      node->src[1]->ne[1], (float *) node->data, node->nb[1] / sizeof(float), qmm_stream(ctx->dev->qmm))) {
-                GGML_LOG_ERROR("MI355X MUL_MAT(%s) with SwiGLU input: %s\n", node->name, qmm_last_error());
-                st = GGML_STATUS_FAILED;
-            }
         } else if (node->op == GGML_OP_MUL_MAT) {
-            st = compute_mul_mat(ctx, cgraph->nodes + i, n_nodes - i, done.data() + i);                      // may hoist later MUL_MATs
+            st = P.issue_mul_mat(i);                                            // may hoist later MUL_MATs
         } else if (node->op == GGML_OP_MUL_MAT_ID) {
-            st = compute_mul_mat_id(ctx, cgraph->nodes + i, n_nodes - i, done.data() + i);
+            st = P.issue_mul_mat_id(i);
         } else if (node->op == GGML_OP_FLASH_ATTN_EXT) {
             st = compute_flash_attn(ctx, node);                                 // opaque to the fusion sites: its own launch
         } else {

@@ -1,10 +1,11 @@
 // mi355x_internal.h — what the plugin's source files share: the context structs, the switches, the timers and every function
-// one file defines and another calls.  The files, by concern (ggml-mi355x.cpp includes the other four: one translation unit):
+// one file defines and another calls.  The files, by concern (ggml-mi355x.cpp includes the other five: one translation unit):
 //   ggml-mi355x.cpp     backend (stream) interface, device, registry, the exported entry points
 //   mi355x_buffers.cpp  device buffer type, pinned host buffer type, planar-weight bookkeeping
 //   mi355x_split.cpp    row split: the split buffer type, compute_mul_mat_split*, the RCCL exchange
 //   mi355x_alias.cpp    aliasing and hoisting rules (ranges_overlap ... hoist_elsewhere)
-//   mi355x_graph.cpp    the graph pass: op gates, analyze_readers, the fusion sites, compute_mul_mat[_id], compute_glue, graph_compute
+//   mi355x_graph.cpp    the graph pass: op gates, analyze_readers, the fusion sites, compute_glue, graph_compute
+//   mi355x_mulmat.cpp   what issues MUL_MAT and MUL_MAT_ID: the group with its hoists and folds, the broadcast form, the expert pair
 // Only ggml headers and the C-ABI are included; all HIP lives in libggml_mi355x_qmm.so.
 #pragma once
 
@@ -157,15 +158,25 @@ struct mi355x_backend_ctx {
     std::vector<const ggml_tensor *> skipped;
     std::vector<char>                done;
     std::vector<const ggml_tensor *> deferred;       // per node: the SILU whose result this MUL consumes in the same launch
-    // RMS_NORM -> MUL(w) held back for the MUL_MATs that read it (few-token batches): they form the normed row while staging
-    struct swiglu_src { const float * gate = nullptr; const float * up = nullptr; int64_t ld_gate = 0, ld_up = 0; };
-    std::vector<swiglu_src>          swiglu_in;      // per node: this ffn_down forms silu(gate) * up in its activation prep (prompt batches)
-    struct norm_req { const ggml_tensor * rn = nullptr, * mul = nullptr, * w = nullptr; int readers = 0; const ggml_tensor * add = nullptr; };   // add: the residual ADD in front of the norm (prompt batches)
-    norm_req                         pending_norm;
     graph_timer                      timer;          // GGML_MI355X_TIMING=1
 };
 
 constexpr int LOOKAHEAD = 12;      // nodes scanned for MUL_MATs on the same src1 (q .. rope .. k .. rope .. v; gate, silu, up)
+
+// what analyze_readers recorded for `t`; NULL when it is no candidate of this graph
+inline const mi355x_backend_ctx::reader_info * find_reader(const mi355x_backend_ctx * ctx, const ggml_tensor * t) {
+    const auto & rd = ctx->readers;
+    auto it = std::lower_bound(rd.begin(), rd.end(), t, [](const mi355x_backend_ctx::reader_info & x, const ggml_tensor * y) { return x.t < y; });
+    return it != rd.end() && it->t == t ? &*it : nullptr;
+}
+inline float rms_eps(const ggml_tensor * rn) { float eps; memcpy(&eps, rn->op_params, sizeof(float)); return eps; }
+// the status of a C-ABI launch that returned rc; a failure is logged as fmt (the names, then the library's error)
+template <class... A> inline enum ggml_status launched(int rc, const char * fmt, A... names) {
+    if (rc) GGML_LOG_ERROR(fmt, names..., qmm_last_error());
+    return rc ? GGML_STATUS_FAILED : GGML_STATUS_SUCCESS;
+}
+// bytes from the first to the last float of N rows of `width` floats, `ld` floats apart
+inline size_t rows_extent(int64_t N, int64_t ld, int64_t width) { return (size_t) ((N - 1) * ld + width) * sizeof(float); }
 
 // ----------------------------------------------------------------------------------------------- ggml-mi355x.cpp
 extern mi355x_device_ctx   g_devs[GGML_MI355X_MAX_DEVICES];
@@ -214,13 +225,63 @@ void * hoist_elsewhere(mi355x_backend_ctx * ctx, const ggml_tensor * d);
 // ----------------------------------------------------------------------------------------------- mi355x_graph.cpp
 bool type_supported(enum ggml_type t);
 bool bf16_weight(const struct ggml_tensor * w);
+bool is_ours(const struct ggml_tensor * t);
 bool supports_mul_mat(const struct ggml_tensor * op);
 bool supports_mul_mat_id(const struct ggml_tensor * op);
 bool supports_glue(const ggml_tensor * node);
 bool supports_flash_attn(const ggml_tensor * node);
 int  glue_op(const ggml_tensor * node);
-bool group_member(const ggml_tensor * t, const ggml_tensor * b, bool split);
 qmm_tensor to_qt(const ggml_tensor * t, const mi355x_backend_ctx * ctx);
+enum ggml_status compute_glue(mi355x_backend_ctx * ctx, const ggml_tensor * node, int op, const ggml_tensor * s0, const ggml_tensor * s1, const ggml_tensor * s2);
 enum ggml_status backend_graph_compute(ggml_backend_t backend, struct ggml_cgraph * cgraph);
+
+// ----------------------------------------------------------------------------------------------- mi355x_mulmat.cpp
+bool group_member(const ggml_tensor * t, const ggml_tensor * b, bool split);
+struct mul_mat_call;
+
+// ---- one graph_compute call (analysis / plan / issue apart) -----------------------------------------------------------
+// analyze_readers() is the analysis; graph_pass holds what the launch sites share.  Every site_* looks at node i and returns 1 when it
+// issued (or deferred) the node, possibly together with later nodes that it marks in done[]; 0 when its pattern is not there (the
+// caller tries the next site, in the order below, and finally the node's own launch); -1 when a launch failed.
+struct graph_pass {
+    mi355x_backend_ctx * ctx;
+    ggml_cgraph * cgraph;
+    int n_nodes;
+    std::vector<char> & done;
+    std::vector<const ggml_tensor *> & deferred;
+    // handed from a site to the MUL_MAT behind it (always the next live node that is issued):
+    // RMS_NORM -> MUL(w), with `add` the residual ADD in front of it (prompt batches), held back for the `readers` MUL_MATs that read it ...
+    struct norm_req { const ggml_tensor * rn = nullptr, * mul = nullptr, * w = nullptr; int readers = 0; const ggml_tensor * add = nullptr; };
+    norm_req pending_norm;
+    // ... and silu(gate) * up held back for the ffn_down `mm`, which forms the product in its activation prep (prompt batches)
+    struct swiglu_src { const float * gate = nullptr; const float * up = nullptr; int64_t ld_gate = 0, ld_up = 0; const ggml_tensor * mm = nullptr; };
+    swiglu_src pending_swiglu;
+    const mi355x_backend_ctx::reader_info * info(const ggml_tensor * t) const { return find_reader(ctx, t); }
+    bool single_use(const ggml_tensor * t) const { const auto * r = info(t); return r && r->uses == 1; }
+    int next_live(int j) const { while (j < n_nodes && (done[j] || is_noop(cgraph->nodes[j]))) ++j; return j; }     // the first node from j on that still runs
+    struct reader_group { int n = 0; int at[4] = { 0, 0, 0, 0 }; bool all = false; };
+    reader_group scan_reader_group(const ggml_tensor * b, int start, int cap) const;
+    int site_deferred_silu_mul(int i, ggml_tensor * node, int gop);
+    int site_hold_silu(int i, ggml_tensor * node, int gop);
+    int site_add_rms_norm(int i, ggml_tensor * node, int gop);
+    int site_rms_norm_mul(int i, ggml_tensor * node, int gop);
+    int site_attention(int i, ggml_tensor * node, int gop);
+    int site_kqv_into_merged_heads(int i, ggml_tensor * node, int gop);
+    int site_moe_combine(int i, ggml_tensor * node, int gop);
+    int site_moe_router(int i, ggml_tensor * node, int gop);
+    int site_rope_kv_attention(int i, ggml_tensor * node, int gop);
+    // mi355x_mulmat.cpp: node i's own launch (GGML_OP_MUL_MAT on a quantized or BF16 weight, GGML_OP_MUL_MAT_ID) and the steps it is made of
+    enum ggml_status issue_mul_mat(int i);
+    enum ggml_status issue_mul_mat_id(int i);
+    void form_group(int i, mul_mat_call & c);
+    enum ggml_status fold_norm(int i, mul_mat_call & c);
+    void fold_swiglu(int i, mul_mat_call & c);
+    void fold_residual(int i, mul_mat_call & c);
+    enum ggml_status launch(int i, const mul_mat_call & c);
+    enum ggml_status issue_mul_mat_broadcast(int i);
+    struct swiglu_match { int silu = -1, mul = -1; };
+    swiglu_match find_swiglu(int i0, int i1, std::vector<const ggml_tensor *> * between) const;
+    int issue_moe_pair_swiglu(int i, int twin, int type);
+};
 
 } // namespace mi355x
