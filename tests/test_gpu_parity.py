@@ -131,6 +131,26 @@ def test_q8_K_double_rounding_ties_bit_exact(qmm, oracle):
     assert rel_rms(got, oracle.mul_mat(Q6_K, w, 512, x, ACT_REF)) < 2e-5
 
 
+def test_q8_1_block_sum_f16_ties_bit_exact(qmm, oracle):
+    """regression: hipcc fused f16(f32(sum * d)) of the Q8_1 block sum into v_fma_mixlo_f16, one rounding of the exact product; in blocks
+    where the f32 product is a tie between two f16 values s came out one f16 ulp off, and every row of a Q4_1 / Q5_1 mat-vec with it
+    (found by test_gpu_moe_routing.py::test_few_pairs_second_slice[q4_1], 1.0e-4 against the 2e-5 bar)"""
+    from helpers import q8_1_sum_tie_rows
+    from oracle.pyoracle import Q4_1, Q5_1
+    x = q8_1_sum_tie_rows(2, 512, seed=4)
+    q, d, s = qmm.quantize_act(9, dev(x))
+    blk = oracle.quantize_act(Q4_1, x).reshape(2, -1, 36)
+    assert np.array_equal(q.cpu().numpy(), blk[:, :, 4:].copy().view(np.int8).reshape(2, -1))
+    want_s = blk[:, :, 2:4].copy().view(np.float16).astype(np.float32).reshape(2, -1)
+    assert np.array_equal(s.cpu().numpy().view(np.uint32), want_s.view(np.uint32))
+    # and through the fused in-kernel quantizer of the mat-vec path
+    import ggml_hexagon_amd.synth as synth
+    for t in (Q4_1, Q5_1):
+        w = synth.synth_weights(t, 64, 512, seed=1, sigma=0.25)
+        got = qmm.mul_mat(t, dev(w), 512, dev(x)).cpu().numpy()
+        assert rel_rms(got, oracle.mul_mat(t, w, 512, x, ACT_REF)) < 2e-5
+
+
 # ----------------------------------------------------------------------------- mat-vec (N <= 8)
 
 @pytest.mark.parametrize("n", [1, 5])
