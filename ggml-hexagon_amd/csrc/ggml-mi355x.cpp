@@ -18,7 +18,7 @@
 // This file: the switches, the backend (stream) interface, the device, the registry and the exported entry points; the other
 // concerns have a file each (mi355x_internal.h lists them).  Only ggml headers and the C-ABI; all HIP lives in libggml_mi355x_qmm.so.
 //
-// The module stays ONE translation unit: this file is what every build recipe compiles, and it includes the five other sections below
+// The module stays ONE translation unit: this file is what every build recipe compiles, and it includes the six other sections below
 // (so the node loop's small helpers inline across them as they did in one file).  Do not hand the sections to the compiler as well.
 
 #include "mi355x_internal.h"
@@ -27,6 +27,7 @@
 #include "mi355x_split.cpp"
 #include "mi355x_alias.cpp"
 #include "mi355x_graph.cpp"
+#include "mi355x_sites.cpp"
 #include "mi355x_mulmat.cpp"
 
 namespace mi355x {

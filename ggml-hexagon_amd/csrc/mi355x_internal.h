@@ -1,10 +1,11 @@
 // mi355x_internal.h — what the plugin's source files share: the context structs, the switches, the timers and every function
-// one file defines and another calls.  The files, by concern (ggml-mi355x.cpp includes the other five: one translation unit):
+// one file defines and another calls.  The files, by concern (ggml-mi355x.cpp includes the other six: one translation unit):
 //   ggml-mi355x.cpp     backend (stream) interface, device, registry, the exported entry points
 //   mi355x_buffers.cpp  device buffer type, pinned host buffer type, planar-weight bookkeeping
 //   mi355x_split.cpp    row split: the split buffer type, compute_mul_mat_split*, the RCCL exchange
 //   mi355x_alias.cpp    aliasing and hoisting rules (ranges_overlap ... hoist_elsewhere)
-//   mi355x_graph.cpp    the graph pass: op gates, analyze_readers, the fusion sites, compute_glue, graph_compute
+//   mi355x_graph.cpp    the graph pass: op gates, compute_glue, flash attention, analyze_readers, graph_compute
+//   mi355x_sites.cpp    the fusion sites: one matcher per motif, the sites (match, alias decisions, issue), the dispatch by op
 //   mi355x_mulmat.cpp   what issues MUL_MAT and MUL_MAT_ID: the group with its hoists and folds, the broadcast form, the expert pair
 // Only ggml headers and the C-ABI are included; all HIP lives in libggml_mi355x_qmm.so.
 #pragma once
@@ -170,6 +171,9 @@ inline const mi355x_backend_ctx::reader_info * find_reader(const mi355x_backend_
     return it != rd.end() && it->t == t ? &*it : nullptr;
 }
 inline float rms_eps(const ggml_tensor * rn) { float eps; memcpy(&eps, rn->op_params, sizeof(float)); return eps; }
+inline const ggml_tensor * root_of(const ggml_tensor * t) { return t->view_src ? t->view_src : t; }      // the tensor whose memory a view shows
+struct sm_params { float scale, max_bias; };
+inline sm_params soft_max_params(const ggml_tensor * sm) { sm_params p; memcpy(&p, sm->op_params, sizeof(p)); return p; }
 // the status of a C-ABI launch that returned rc; a failure is logged as fmt (the names, then the library's error)
 template <class... A> inline enum ggml_status launched(int rc, const char * fmt, A... names) {
     if (rc) GGML_LOG_ERROR(fmt, names..., qmm_last_error());
@@ -232,17 +236,29 @@ bool supports_glue(const ggml_tensor * node);
 bool supports_flash_attn(const ggml_tensor * node);
 int  glue_op(const ggml_tensor * node);
 qmm_tensor to_qt(const ggml_tensor * t, const mi355x_backend_ctx * ctx);
+int  op_compute(mi355x_backend_ctx * ctx, int op, const qmm_tensor * s0, const qmm_tensor * s1, const qmm_tensor * s2, const qmm_tensor * d);
 enum ggml_status compute_glue(mi355x_backend_ctx * ctx, const ggml_tensor * node, int op, const ggml_tensor * s0, const ggml_tensor * s1, const ggml_tensor * s2);
+enum { ATTN_DECODE = 1, ATTN_PREFILL = 2 };
+int  issue_attention(mi355x_backend_ctx * ctx, const qmm_tensor & q, const qmm_tensor & k, const qmm_tensor & v, const qmm_tensor & m, const qmm_tensor & d,
+                     float scale, const char * what, const char * name, bool probe_prefill);
 enum ggml_status backend_graph_compute(ggml_backend_t backend, struct ggml_cgraph * cgraph);
 
 // ----------------------------------------------------------------------------------------------- mi355x_mulmat.cpp
 bool group_member(const ggml_tensor * t, const ggml_tensor * b, bool split);
+// ----------------------------------------------------------------------------------------------- mi355x_sites.cpp
+int  fused_pair(const ggml_tensor * n0, const ggml_tensor * n1, const ggml_tensor ** other);
 struct mul_mat_call;
 
 // ---- one graph_compute call (analysis / plan / issue apart) -----------------------------------------------------------
-// analyze_readers() is the analysis; graph_pass holds what the launch sites share.  Every site_* looks at node i and returns 1 when it
-// issued (or deferred) the node, possibly together with later nodes that it marks in done[]; 0 when its pattern is not there (the
-// caller tries the next site, in the order below, and finally the node's own launch); -1 when a launch failed.
+// analyze_readers() is the analysis; graph_pass holds what the launch sites share.  A fusion site (mi355x_sites.cpp) has three steps:
+//   match   a match_* member, const: it reads the graph, done[] and the reader analysis and fills a record of node indices (plus the
+//           variant chosen); it launches nothing and marks nothing.  Each motif has one matcher, shared by the sites that contain it.
+//   alias   early_write_ok / can_hoist / hoist_elsewhere on the matched nodes, in a fixed order: hoist_elsewhere is the one step with a
+//           side effect (it claims scratch and adds a redirect that every later to_qt follows, also when the library then declines).
+//   issue   operands through to_qt, the library's *_supported probe, the one call through launched(), the debug line, done[] from the record.
+// offer_to_sites(i, gop) offers glue node i to the sites that can start at its op (the table and its order: at its definition).  It and
+// every site_*(i) return 1 when node i was issued (or held back), possibly together with later nodes marked in done[]; 0 when no
+// pattern is there (the caller issues the node alone); -1 when a launch failed.
 struct graph_pass {
     mi355x_backend_ctx * ctx;
     ggml_cgraph * cgraph;
@@ -261,15 +277,33 @@ struct graph_pass {
     int next_live(int j) const { while (j < n_nodes && (done[j] || is_noop(cgraph->nodes[j]))) ++j; return j; }     // the first node from j on that still runs
     struct reader_group { int n = 0; int at[4] = { 0, 0, 0, 0 }; bool all = false; };
     reader_group scan_reader_group(const ggml_tensor * b, int start, int cap) const;
-    int site_deferred_silu_mul(int i, ggml_tensor * node, int gop);
-    int site_hold_silu(int i, ggml_tensor * node, int gop);
-    int site_add_rms_norm(int i, ggml_tensor * node, int gop);
-    int site_rms_norm_mul(int i, ggml_tensor * node, int gop);
-    int site_attention(int i, ggml_tensor * node, int gop);
-    int site_kqv_into_merged_heads(int i, ggml_tensor * node, int gop);
-    int site_moe_combine(int i, ggml_tensor * node, int gop);
-    int site_moe_router(int i, ggml_tensor * node, int gop);
-    int site_rope_kv_attention(int i, ggml_tensor * node, int gop);
+    // mi355x_sites.cpp.  The match records hold node indices, -1 where a part is absent or nothing matched
+    struct attn_chain    { int kq = -1, sm = -1, kqv = -1, pm = -1, ct = -1; float scale = 0; };
+    struct add_norm      { int add = -1, rn = -1, mul = -1; const ggml_tensor * w = nullptr; };
+    enum router_form     { ROUTER_NONE = 0, ROUTER, ROUTER_LOGITS, ROUTER_LOGITS_NORM };       // what the launch computes besides the router itself
+    struct router_match  { int nrm = -1, nmul = -1, lgt = -1, sm = -1, argsort = -1, get_rows = -1, sum_rows = -1, div = -1;
+                           const ggml_tensor * nwgt = nullptr; int64_t n_used = 0; router_form form = ROUTER_NONE; };
+    struct combine_match { int U = 0; int adds[63]; };                                        // U used experts (0: no match), their U - 1 ADDs
+    struct rope_kv_match { int rk = -1, ck = -1, cv = -1; };                                  // rope(k), its store, v's store
+    attn_chain    match_attention(int kq, int from, int last) const;
+    add_norm      match_add_norm(int ja, const ggml_tensor * operand) const;
+    router_match  match_router(int entry, std::vector<const ggml_tensor *> & skipped) const;
+    combine_match match_moe_combine(int i) const;
+    rope_kv_match match_rope_kv(int i) const;
+    struct add_norm_operands { qmm_tensor a, b, w, sum, d; };
+    add_norm_operands marshal_add_norm(const ggml_tensor * add, const ggml_tensor * mul, const ggml_tensor * w) const;
+    enum ggml_status launch_add_rms_norm(const add_norm_operands & o, const ggml_tensor * add, const ggml_tensor * rn);     // (also fold_norm's way out)
+    int issue_router(int entry, const router_match & r);
+    int offer_to_sites(int i, int gop);
+    int site_deferred_silu_mul(int i);
+    int site_hold_silu(int i);
+    int site_add_rms_norm(int i);
+    int site_rms_norm_mul(int i);
+    int site_attention(int i);
+    int site_kqv_into_merged_heads(int i);
+    int site_moe_combine(int i);
+    int site_moe_router(int i);
+    int site_rope_kv_attention(int i);
     // mi355x_mulmat.cpp: node i's own launch (GGML_OP_MUL_MAT on a quantized or BF16 weight, GGML_OP_MUL_MAT_ID) and the steps it is made of
     enum ggml_status issue_mul_mat(int i);
     enum ggml_status issue_mul_mat_id(int i);

@@ -111,9 +111,8 @@ enum ggml_status graph_pass::fold_norm(int i, mul_mat_call & c) {
     // the graph's three nodes after all, as the site would have run them
     // TODO(advisor r3): the site's own launch asks early_write_ok of `mul` against the ADD's operands (e_ok); neither the
     // hold-back test nor this path does
-    const qmm_tensor a = to_qt(pn.add->src[0], ctx), bb = to_qt(pn.add->src[1], ctx), w = to_qt(pn.w, ctx), sum = to_qt(pn.add, ctx), d = to_qt(pn.mul, ctx);
     if (dbg()) fprintf(stderr, "fusion declined: add + norm (%s) into the prep of %s (group of %d of %d readers)\n", pn.add->name, dst->name, c.n, pn.readers);
-    return launched(qmm_op_add_rms_norm(q, &a, &bb, &w, &sum, &d, rms_eps(pn.rn), qmm_stream(q)), "MI355X ADD+RMS_NORM(%s): %s\n", pn.add->name);
+    return launch_add_rms_norm(marshal_add_norm(pn.add, pn.mul, pn.w), pn.add, pn.rn);
 }
 
 // The SwiGLU behind a gate / up pair, nodes i0 and i1 (build_ffn, build_moe_ffn): a SILU of one result, then the MUL of it with the

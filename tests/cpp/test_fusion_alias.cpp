@@ -1,4 +1,4 @@
-// test_fusion_alias.cpp — the aliasing cases behind the plugin's multi-node launches (csrc/ggml-mi355x.cpp early_write_ok).
+// test_fusion_alias.cpp — the aliasing cases behind the plugin's multi-node launches (csrc/mi355x_alias.cpp early_write_ok, asked by csrc/mi355x_sites.cpp).
 // A fused launch writes a LATER node's buffer at an EARLIER point.  ggml-alloc may legally give that later node the block of a tensor
 // that is dead by then in the graph's order but is still an OPERAND of the fused launch: the residual ADD behind wo placed on wo's
 // src1, the SwiGLU product placed on ffn_norm's output, q placed on the un-normed row whose norm the mat-vec forms itself, the
