@@ -9,6 +9,7 @@ from . import build as _build
 
 Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 2, 8, 12, 13, 14, 15
 Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, IQ4_NL, IQ4_XS = 3, 6, 7, 10, 11, 20, 23
+IQ3_XXS, IQ3_S = 18, 21  # need their grids first: Qmm.set_codebook
 BF16 = 30               # unquantized rows of K bf16 values (K % 32 == 0, rows on 16-byte boundaries): mul_mat, mul_mat_group, dequantize
 ACT_REF, ACT_X86 = 0, 1
 PREC_BF16, PREC_F16_Q8, PREC_Q8_EXACT = 0, 1, 2
@@ -20,7 +21,7 @@ EXPORTS = [
     "qmm_device_info", "qmm_set_act_mode", "qmm_set_precision", "qmm_q8_exact_supported", "qmm_malloc", "qmm_free", "qmm_host_malloc", "qmm_host_free", "qmm_memcpy_h2d",
     "qmm_memcpy_d2h", "qmm_memcpy_d2d", "qmm_memset", "qmm_synchronize", "qmm_memcpy2d_d2d", "qmm_event_create",
     "qmm_event_destroy", "qmm_event_record", "qmm_stream_wait_event", "qmm_event_synchronize", "qmm_event_create_timing", "qmm_event_elapsed_ms", "qmm_memcpy_h2d_async",
-    "qmm_memcpy_d2h_async", "qmm_row_size", "qmm_planar_type", "qmm_repack_rows", "qmm_dequantize",
+    "qmm_memcpy_d2h_async", "qmm_set_codebook", "qmm_row_size", "qmm_planar_type", "qmm_repack_rows", "qmm_dequantize",
     "qmm_quantize_act", "qmm_mul_mat", "qmm_mul_mat_group", "qmm_mul_mat_group_ex", "qmm_mul_mat_group_norm_supported", "qmm_mul_mat_swiglu_in", "qmm_mul_mat_id", "qmm_mul_mat_id_pair", "qmm_mul_mat_id_swiglu_supported", "qmm_mul_mat_id_swiglu",
     "qmm_chain_begin", "qmm_chain_flush", "qmm_chain_end", "qmm_chain_stats", "qmm_chain_debug", "qmm_trace_begin", "qmm_trace_end",
     "qmm_comm_create", "qmm_comm_destroy", "qmm_comm_size", "qmm_comm_broadcast", "qmm_comm_gather", "qmm_comm_all_gather",
@@ -121,6 +122,8 @@ def load_library() -> C.CDLL:
     lib.qmm_memcpy_d2h_async.argtypes = [v, v, v, sz, v]
     lib.qmm_row_size.restype = sz
     lib.qmm_row_size.argtypes = [i32, i64]
+    if hasattr(lib, "qmm_set_codebook"):       # (profiles/tools load the library of an older commit beside this one: it has none)
+        lib.qmm_set_codebook.argtypes = [v, i32, v, i32]
     lib.qmm_dequantize.argtypes = [v, i32, v, i64, i64, i64, v, v]
     lib.qmm_planar_type.argtypes = [i32, i64, i64]
     lib.qmm_repack_rows.argtypes = [v, i32, v, i64, i64, i64, i32, v]
@@ -201,6 +204,13 @@ class Qmm:
 
     def row_size(self, t, k):
         return self.lib.qmm_row_size(t, k)
+
+    def set_codebook(self, t, entries):
+        """the grid of IQ3_XXS (256 entries) or IQ3_S (512): uint32 values, byte j of an entry = the magnitude of weight j.  The
+        library has none of its own; derive it from ggml (tests/iq3_refs.py shows how) and hand it to every context"""
+        import numpy as np
+        e = np.ascontiguousarray(entries, dtype=np.uint32)
+        self._chk(self.lib.qmm_set_codebook(self.ctx, t, e.ctypes.data, e.size))
 
     # --- chains: one-token mul_mat_group[_ex] calls between begin and end are recorded and go out as persistent launches
     def chain_begin(self):

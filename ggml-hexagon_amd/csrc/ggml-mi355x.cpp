@@ -52,6 +52,60 @@ mi355x_device_ctx      g_devs[GGML_MI355X_MAX_DEVICES];
 ggml_backend_device    g_devices[GGML_MI355X_MAX_DEVICES];
 int                    g_ndev = 0;
 
+// ----------------------------------------------------------------------------------------------- codebooks (IQ3_XXS, IQ3_S)
+
+// The grids of the two 3-bit i-quants are tables of ggml's source; this module carries none.  It reads them out of the ggml it is
+// loaded into, through the type's own to_float on blocks crafted so that every float IS one byte of one grid entry:
+//   IQ3_XXS (98-byte block: f16 d | 64 index bytes | 8 sign / scale words): d = 4.0 and all words 0 make the sub-block scale
+//           d * (0.5 + 0) * 0.5 = 1 and every sign +; block b holds the indices 64 b .. 64 b + 63;
+//   IQ3_S   (110-byte block: f16 d | 64 index bytes | 8 qh bytes | 32 sign bytes | 4 scale bytes): d = 1.0, scales 0 (1 + 2 * 0 = 1),
+//           signs 0; block b holds the low 8 bits of 64 b .. 64 b + 63, the ninth bit (qh) is set in blocks 4 .. 7.
+// The four floats of group i of block b are the bytes of entry 64 b + i.  A table is used only if every byte is an integer in 1 .. 255.
+bool derive_codebook(enum ggml_type type, std::vector<uint32_t> & grid) {
+    const struct ggml_type_traits * tt = ggml_get_type_traits(type);
+    const bool xxs = type == GGML_TYPE_IQ3_XXS;
+    const size_t bs = xxs ? 98 : 110, nblk = xxs ? 4 : 8;
+    if (!tt || !tt->to_float || tt->blck_size != 256 || tt->type_size != bs) return false;
+    std::vector<uint8_t> blocks(nblk * bs, 0);
+    for (size_t b = 0; b < nblk; ++b) {
+        uint8_t * blk = blocks.data() + b * bs;
+        blk[0] = 0x00;  blk[1] = xxs ? 0x44 : 0x3c;                  // f16 4.0 / 1.0, little-endian
+        for (int i = 0; i < 64; ++i) blk[2 + i] = (uint8_t) (64 * b + i);
+        if (!xxs && b >= 4) memset(blk + 66, 0xff, 8);
+    }
+    std::vector<float> out(nblk * 256);
+    tt->to_float(blocks.data(), out.data(), (int64_t) out.size());
+    grid.assign(nblk * 64, 0);
+    for (size_t e = 0; e < grid.size(); ++e)
+        for (int j = 0; j < 4; ++j) {
+            const float v = out[4 * e + j];
+            if (!(v >= 1.0f && v <= 255.0f) || v != (float) (int) v) return false;
+            grid[e] |= (uint32_t) (int) v << (8 * j);
+        }
+    return true;
+}
+
+// every device gets both grids; a type counts as supported only if all of them took it
+void set_codebooks() {
+    const enum ggml_type types[2] = { GGML_TYPE_IQ3_XXS, GGML_TYPE_IQ3_S };
+    for (int k = 0; k < 2; ++k) {
+        g_codebook_ok[k] = false;
+        if (!qmm_set_codebook || g_ndev == 0) continue;              // a kernel library without the entry point: the types stay with the CPU
+        std::vector<uint32_t> grid;
+        if (!derive_codebook(types[k], grid)) {
+            GGML_LOG_WARN("MI355X: no usable grid from ggml's %s dequantizer; the type stays on the CPU\n", ggml_type_name(types[k]));
+            continue;
+        }
+        bool ok = true;
+        for (int i = 0; i < g_ndev && ok; ++i)
+            if (qmm_set_codebook(g_devs[i].qmm, (int) types[k], grid.data(), (int) grid.size())) {
+                GGML_LOG_WARN("MI355X: %s: %s; the type stays on the CPU\n", ggml_type_name(types[k]), qmm_last_error());
+                ok = false;
+            }
+        g_codebook_ok[k] = ok;
+    }
+}
+
 // ----------------------------------------------------------------------------------------------- timing (GGML_MI355X_TIMING=1)
 
 void graph_timer::begin(const ggml_cgraph * cgraph) {
@@ -350,6 +404,7 @@ ggml_backend_reg_t ggml_backend_mi355x_reg(void) {
             d.buft = ggml_backend_buffer_type{ buft_iface, &g_devices[g_ndev], &d };
             ++g_ndev;
         }
+        set_codebooks();
         GGML_LOG_INFO("MI355X backend: %d device(s); quantized MUL_MAT / MUL_MAT_ID (Q4_0 Q8_0 Q4_K Q5_K Q6_K)%s\n", g_ndev,
                       !sw().glue ? "" : " and the glue ops of a transformer layer");
     });

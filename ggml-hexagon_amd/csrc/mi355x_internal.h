@@ -15,6 +15,8 @@
 #include "ggml-impl.h"
 #include "ggml_mi355x_qmm.h"
 #include "ggml_mi355x_ops.h"
+// the module must load against a kernel library that has no qmm_set_codebook (ggml opens backends with RTLD_NOW): a weak reference, null then
+#pragma weak qmm_set_codebook
 #include "qmm_switches.h"
 #include "qmm_matvec_plan.h"
 
@@ -228,6 +230,7 @@ void * hoist_elsewhere(mi355x_backend_ctx * ctx, const ggml_tensor * d);
 
 // ----------------------------------------------------------------------------------------------- mi355x_graph.cpp
 bool type_supported(enum ggml_type t);
+extern bool g_codebook_ok[2];                                        // IQ3_XXS, IQ3_S: every device holds the grid (mi355x_graph.cpp)
 bool bf16_weight(const struct ggml_tensor * w);
 bool is_ours(const struct ggml_tensor * t);
 bool supports_mul_mat(const struct ggml_tensor * op);

@@ -73,8 +73,9 @@ static MatvecGroup matvec_group(const qmm_weight * ws, const int * idx, const in
     return g;
 }
 
-static int check_mm(int type, const void * w, int64_t rb, int64_t K, const float * x, int64_t ldx, const char * who) {
+static int check_mm(const qmm_ctx * c, int type, const void * w, int64_t rb, int64_t K, const float * x, int64_t ldx, const char * who) {
     if (!type_known(type)) return fail(QMM_EUNSUPPORTED, "%s: type %d not supported", who, type);
+    if (const int rc = need_codebook(c, type, who)) return rc;
     if (K <= 0 || K % type_blck(type)) return fail(QMM_EUNSUPPORTED, "%s: K=%lld must be a multiple of %d", who, (long long) K, type_blck(type));
     if (rb < (int64_t) qmm_row_size(type, K)) return fail(QMM_EINVAL, "%s: weight row stride %lld < row size", who, (long long) rb);
     if ((uintptr_t) x % 16 || ldx % 4 || ldx < K) return fail(QMM_EINVAL, "%s: src1 must be 16-byte aligned with ldx %% 4 == 0", who);
@@ -485,6 +486,28 @@ size_t qmm_row_size(int type, int64_t k) {
     return (size_t) (k / type_blck(type)) * type_tsize(type);
 }
 
+// ------------------------------------------------------------------------------------------- codebooks
+
+int qmm_set_codebook(qmm_ctx * c, int type, const uint32_t * entries, int n_entries) {
+    if (!c || !entries) return fail(QMM_EINVAL, "qmm_set_codebook: NULL context or table");
+    if (!type_codebook(type)) return fail(QMM_EINVAL, "qmm_set_codebook: type %d takes no codebook (IQ3_XXS = %d, IQ3_S = %d do)", type, T_IQ3_XXS, T_IQ3_S);
+    if (n_entries != type_codebook(type)) return fail(QMM_EINVAL, "qmm_set_codebook: type %d has %d entries, not %d", type, type_codebook(type), n_entries);
+    // the units hold a magnitude with its sign as an int8 (neg4, qmm_device.hiph)
+    for (int i = 0; i < n_entries; ++i)
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t v = (entries[i] >> (8 * j)) & 0xffu;
+            if (v < 1 || v > 127) return fail(QMM_EUNSUPPORTED, "qmm_set_codebook: entry %d holds %u; the kernels take magnitudes in 1 .. 127", i, v);
+        }
+    HIP_TRY(hipSetDevice(c->device));
+    QMM_CHAIN_FLUSH(c);
+    HIP_TRY(hipDeviceSynchronize());                             // no launch in flight reads a table while it changes
+    const int off = type == T_IQ3_S ? 256 : 0;
+    HIP_TRY(iq3_grid_upload(off, entries, n_entries));
+    if (const int rc = qmm_internal_ops_codebook(off, entries, n_entries)) return rc;
+    c->codebook[codebook_slot(type)] = true;
+    return QMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------- dequantize
 
 int qmm_dequantize(qmm_ctx * c, int type, const void * w, int64_t rb, int64_t rows, int64_t K, float * dst, void * st) {
@@ -496,6 +519,7 @@ int qmm_dequantize(qmm_ctx * c, int type, const void * w, int64_t rb, int64_t ro
         return run_bf16_widen(c->s(st), w, rb, rows, K, dst);
     }
     if (!c || !type_known(type)) return fail(QMM_EINVAL, "qmm_dequantize: bad ctx/type %d", type);
+    if (const int rc = need_codebook(c, type, "qmm_dequantize")) return rc;
     if (K <= 0 || K % type_blck(type)) return fail(QMM_EINVAL, "qmm_dequantize: K=%lld", (long long) K);
     if (rb < (int64_t) qmm_row_size(type, K)) return fail(QMM_EINVAL, "qmm_dequantize: row stride too small");
     if ((uintptr_t) dst % 16) return fail(QMM_EINVAL, "qmm_dequantize: dst must be 16-byte aligned");
@@ -597,7 +621,7 @@ static int mul_mat_group_impl(qmm_ctx * c, const qmm_weight * ws, int nw, int64_
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->s(stream);
     for (int i = 0; i < nw; ++i) {
-        int rc = check_mm(ws[i].type, ws[i].w, ws[i].w_row_bytes, K, x, ldx, "qmm_mul_mat");
+        int rc = check_mm(c, ws[i].type, ws[i].w, ws[i].w_row_bytes, K, x, ldx, "qmm_mul_mat");
         if (rc) return rc;
         if (ws[i].M < 0 || ws[i].ldd < ws[i].M) return fail(QMM_EINVAL, "qmm_mul_mat: ldd < M");
     }
@@ -688,7 +712,7 @@ static int check_mm_id(const qmm_ctx * c, const char * who, bool second, int typ
                        int64_t b_nb1, int64_t b_nb2, int64_t ids_nb1, int64_t n_used, int64_t d_nb1, int64_t d_nb2) {
     if (!c) return fail(QMM_EINVAL, "null ctx");
     if (!second) return fail(QMM_EINVAL, "%s: second tensor missing", who);
-    const int rc = check_mm(type, as, rb, K, b, K, who);
+    const int rc = check_mm(c, type, as, rb, K, b, K, who);
     if (rc) return rc;
     if (b_nb1 % 16 || b_nb2 % 16 || ids_nb1 % 4 || d_nb1 % 4 || d_nb2 % 4 || expert_bytes % 2 || (ne11 != 1 && ne11 != n_used)) return fail(QMM_EINVAL, "%s: strides / ne11", who);
     return QMM_OK;

@@ -1099,6 +1099,12 @@ int run_glue(qmm_ctx * ctx, hipStream_t st, const GluePlan & p, const GlueArgs &
 
 } // namespace
 
+// qmm_set_codebook (qmm_api.hip) writes both code objects' tables: this one's serves get_rows_q_kernel
+int qmm_internal_ops_codebook(int off, const uint32_t * entries, int n) {
+    HIP_TRY(iq3_grid_upload(off, entries, n));
+    return QMM_OK;
+}
+
 #include "qmm_attn.hiph"         // the attention kernels, their launch executor and entry points
 
 extern "C" {
@@ -1108,6 +1114,7 @@ int qmm_op_supported(int op, const qmm_tensor * a, const qmm_tensor * b, const q
 int qmm_op_compute(qmm_ctx * ctx, int op, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * c, const qmm_tensor * d, void * stream) {
     if (!ctx || !d) return fail(QMM_EINVAL, "qmm_op_compute: NULL context or dst");
     if (!sup_op(op, a, b, c, d)) return fail(QMM_EUNSUPPORTED, "qmm_op_compute: op %d with these types / shapes / strides is not implemented", op);
+    if (op == QMM_OP_GET_ROWS) { const int rc = need_codebook(ctx, a->type, "qmm_op_compute(GET_ROWS)"); if (rc) return rc; }
     HIP_TRY(hipSetDevice(ctx->device));
     QMM_CHAIN_FLUSH(ctx);
     GlueArgs g;

@@ -140,6 +140,19 @@ QMM_API int          qmm_event_record(qmm_ctx * ctx, qmm_event * ev, void * stre
 QMM_API int          qmm_stream_wait_event(qmm_ctx * ctx, void * stream, qmm_event * ev);
 QMM_API int          qmm_event_synchronize(qmm_ctx * ctx, qmm_event * ev);              /* host waits for the event */
 
+/* IQ3_XXS = 18 and IQ3_S = 21 (ggml/src/ggml-common.h:365-380): four weights per index into a grid of packed magnitudes.  The grids are
+ * tables of ggml's source and are not part of this library: the caller derives them at run time (the plugin from the type's to_float on
+ * crafted blocks) and hands them to every context that shall run the type.  entries: HOST memory, n_entries = 256 (type 18) or 512
+ * (type 21) u32, byte j of an entry = bits 8j .. 8j+7 = the magnitude of weight j, each in 1 .. 127 (QMM_EUNSUPPORTED otherwise: the
+ * kernels hold a magnitude with its sign as an int8); any other type or count is QMM_EINVAL.  The call copies the table to the context's
+ * device and returns when it is there; call it outside stream capture, again with the same table if you like.  Until it has been
+ * called, qmm_row_size answers for both types (pure geometry: K/256 * 98 and K/256 * 110), and every launch on them
+ * (qmm_mul_mat*, qmm_mul_mat_id*, qmm_dequantize, QMM_OP_GET_ROWS) returns QMM_EUNSUPPORTED with "codebook" in qmm_last_error().
+ * Both types: Q8_K activations; few tokens on matvec_kernel<type, n> (a group with other types runs as consecutive launches), prompt
+ * batches on mfma_kernel<type, rows> in QMM_PREC_F16_Q8 and QMM_PREC_BF16; qmm_planar_type, qmm_q8_exact_supported and
+ * qmm_mul_mat_group_norm_supported return 0; inside a chain recording they launch what was recorded and then themselves, directly. */
+QMM_API int          qmm_set_codebook(qmm_ctx * ctx, int type, const uint32_t * entries, int n_entries);
+
 /* bytes of one weight row of k values; 0 for a type that is no weight type or a k off its block size (BF16: 2 k, k a multiple of 32) */
 QMM_API size_t       qmm_row_size(int type, int64_t k);
 
