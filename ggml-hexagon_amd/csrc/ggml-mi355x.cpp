@@ -52,7 +52,7 @@ mi355x_device_ctx      g_devs[GGML_MI355X_MAX_DEVICES];
 ggml_backend_device    g_devices[GGML_MI355X_MAX_DEVICES];
 int                    g_ndev = 0;
 
-// ----------------------------------------------------------------------------------------------- codebooks (IQ3_XXS, IQ3_S)
+// ----------------------------------------------------------------------------------------------- codebooks (IQ3_XXS, IQ3_S, IQ2_XS, IQ2_S)
 
 // The grids of the two 3-bit i-quants are tables of ggml's source; this module carries none.  It reads them out of the ggml it is
 // loaded into, through the type's own to_float on blocks crafted so that every float IS one byte of one grid entry:
@@ -60,35 +60,52 @@ int                    g_ndev = 0;
 //           d * (0.5 + 0) * 0.5 = 1 and every sign +; block b holds the indices 64 b .. 64 b + 63;
 //   IQ3_S   (110-byte block: f16 d | 64 index bytes | 8 qh bytes | 32 sign bytes | 4 scale bytes): d = 1.0, scales 0 (1 + 2 * 0 = 1),
 //           signs 0; block b holds the low 8 bits of 64 b .. 64 b + 63, the ninth bit (qh) is set in blocks 4 .. 7.
-// The four floats of group i of block b are the bytes of entry 64 b + i.  A table is used only if every byte is an integer in 1 .. 255.
+// The four floats of group i of block b are the bytes of entry 64 b + i.  A table is used only if every float is an integer in 1 .. 255.
+//
+// The two 2-bit i-quants with eight weights per entry, the same way: d = 8.0, scales 0 and every sign + make the sub-block scale
+// 8 * (0.5 + 0) * 0.25 = 1;
+//   IQ2_XS  (74-byte block: f16 d | 32 u16 of a 9-bit index and a 7-bit sign index | 8 scale bytes): 16 blocks, qs[i] of block b = 32 b + i;
+//   IQ2_S   (82-byte block: f16 d | 32 index low bytes | 32 sign bytes | 8 qh bytes | 8 scale bytes): 32 blocks, low byte (32 b + i) & 0xff,
+//           qh[ib] = 0x55 * (32 b >> 8): all four entries of a sub-block get the block's two high index bits.
+// The eight floats of entry i of block b are the bytes of entry e = 32 b + i: the words 2e (weights 0 .. 3) and 2e + 1 (4 .. 7).
+// Every four consecutive floats are one table word, byte j = float j.
 bool derive_codebook(enum ggml_type type, std::vector<uint32_t> & grid) {
     const struct ggml_type_traits * tt = ggml_get_type_traits(type);
-    const bool xxs = type == GGML_TYPE_IQ3_XXS;
-    const size_t bs = xxs ? 98 : 110, nblk = xxs ? 4 : 8;
+    const bool xxs = type == GGML_TYPE_IQ3_XXS, iq3 = xxs || type == GGML_TYPE_IQ3_S, xs = type == GGML_TYPE_IQ2_XS;
+    const size_t bs = xxs ? 98 : iq3 ? 110 : xs ? 74 : 82, nblk = xxs ? 4 : iq3 ? 8 : xs ? 16 : 32;
     if (!tt || !tt->to_float || tt->blck_size != 256 || tt->type_size != bs) return false;
     std::vector<uint8_t> blocks(nblk * bs, 0);
     for (size_t b = 0; b < nblk; ++b) {
         uint8_t * blk = blocks.data() + b * bs;
-        blk[0] = 0x00;  blk[1] = xxs ? 0x44 : 0x3c;                  // f16 4.0 / 1.0, little-endian
-        for (int i = 0; i < 64; ++i) blk[2 + i] = (uint8_t) (64 * b + i);
-        if (!xxs && b >= 4) memset(blk + 66, 0xff, 8);
+        blk[0] = 0x00;  blk[1] = xxs ? 0x44 : iq3 ? 0x3c : 0x48;     // f16 4.0 / 1.0 / 8.0, little-endian
+        if (iq3) {
+            for (int i = 0; i < 64; ++i) blk[2 + i] = (uint8_t) (64 * b + i);
+            if (!xxs && b >= 4) memset(blk + 66, 0xff, 8);
+        } else {
+            for (int i = 0; i < 32; ++i) {
+                const unsigned e = (unsigned) (32 * b + i);
+                if (xs) { blk[2 + 2 * i] = (uint8_t) (e & 0xff);  blk[3 + 2 * i] = (uint8_t) (e >> 8); }
+                else      blk[2 + i] = (uint8_t) (e & 0xff);
+            }
+            if (!xs) memset(blk + 66, (int) (0x55 * ((32 * b) >> 8)), 8);
+        }
     }
     std::vector<float> out(nblk * 256);
     tt->to_float(blocks.data(), out.data(), (int64_t) out.size());
     grid.assign(nblk * 64, 0);
-    for (size_t e = 0; e < grid.size(); ++e)
+    for (size_t w = 0; w < grid.size(); ++w)
         for (int j = 0; j < 4; ++j) {
-            const float v = out[4 * e + j];
+            const float v = out[4 * w + j];
             if (!(v >= 1.0f && v <= 255.0f) || v != (float) (int) v) return false;
-            grid[e] |= (uint32_t) (int) v << (8 * j);
+            grid[w] |= (uint32_t) (int) v << (8 * j);
         }
     return true;
 }
 
-// every device gets both grids; a type counts as supported only if all of them took it
+// every device gets all four grids; a type counts as supported only if all of them took it
 void set_codebooks() {
-    const enum ggml_type types[2] = { GGML_TYPE_IQ3_XXS, GGML_TYPE_IQ3_S };
-    for (int k = 0; k < 2; ++k) {
+    const enum ggml_type types[4] = { GGML_TYPE_IQ3_XXS, GGML_TYPE_IQ3_S, GGML_TYPE_IQ2_XS, GGML_TYPE_IQ2_S };
+    for (int k = 0; k < 4; ++k) {
         g_codebook_ok[k] = false;
         if (!qmm_set_codebook || g_ndev == 0) continue;              // a kernel library without the entry point: the types stay with the CPU
         std::vector<uint32_t> grid;

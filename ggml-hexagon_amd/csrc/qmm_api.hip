@@ -490,7 +490,9 @@ size_t qmm_row_size(int type, int64_t k) {
 
 int qmm_set_codebook(qmm_ctx * c, int type, const uint32_t * entries, int n_entries) {
     if (!c || !entries) return fail(QMM_EINVAL, "qmm_set_codebook: NULL context or table");
-    if (!type_codebook(type)) return fail(QMM_EINVAL, "qmm_set_codebook: type %d takes no codebook (IQ3_XXS = %d, IQ3_S = %d do)", type, T_IQ3_XXS, T_IQ3_S);
+    if (!type_codebook(type))
+        return fail(QMM_EINVAL, "qmm_set_codebook: type %d takes no codebook (IQ2_XS = %d, IQ3_XXS = %d, IQ3_S = %d, IQ2_S = %d do)", type, T_IQ2_XS, T_IQ3_XXS, T_IQ3_S, T_IQ2_S);
+    // (n_entries counts 32-bit words: an IQ2 entry of eight magnitudes is two of them)
     if (n_entries != type_codebook(type)) return fail(QMM_EINVAL, "qmm_set_codebook: type %d has %d entries, not %d", type, type_codebook(type), n_entries);
     // the units hold a magnitude with its sign as an int8 (neg4, qmm_device.hiph)
     for (int i = 0; i < n_entries; ++i)
@@ -501,9 +503,8 @@ int qmm_set_codebook(qmm_ctx * c, int type, const uint32_t * entries, int n_entr
     HIP_TRY(hipSetDevice(c->device));
     QMM_CHAIN_FLUSH(c);
     HIP_TRY(hipDeviceSynchronize());                             // no launch in flight reads a table while it changes
-    const int off = type == T_IQ3_S ? 256 : 0;
-    HIP_TRY(iq3_grid_upload(off, entries, n_entries));
-    if (const int rc = qmm_internal_ops_codebook(off, entries, n_entries)) return rc;
+    HIP_TRY(codebook_upload(type, entries, n_entries));
+    if (const int rc = qmm_internal_ops_codebook(type, entries, n_entries)) return rc;
     c->codebook[codebook_slot(type)] = true;
     return QMM_OK;
 }

@@ -59,7 +59,7 @@ struct qmm_ctx {
     bool        chain_attr_set = false;      // the kernel's dynamic-LDS limit has been raised on this device
     int         chain_checked = 0;   // chain_launches when the error word was last read
     hipStream_t chain_stream = nullptr;         // stream of the recorded steps
-    bool        codebook[2] = { false, false };   // qmm_set_codebook: this context has IQ3_XXS's / IQ3_S's grid (until then the types are refused)
+    bool        codebook[4] = { false, false, false, false };   // qmm_set_codebook: this context has the grid of IQ3_XXS / IQ3_S / IQ2_XS / IQ2_S (codebook_slot; until then the type is refused)
     char        name[128] = {0};
     // qmm_trace_begin / qmm_trace_end: while set, every kernel launch of the MUL_MAT path, of the glue launches behind qmm_op_compute /
     // qmm_op_add_rms_norm (run_glue of qmm_ops.hip) and of the attention entry points (qmm_attn.hiph) appends its label here (host side only; bench.py buckets its roofline by the kernels a call actually
@@ -78,8 +78,8 @@ struct qmm_ctx {
 // launches what a recording context has collected (qmm_chain_begin); every entry point that queues other work calls it first, so
 // stream order is the order of the calls whether or not a chain is being recorded.  Defined in qmm_api.hip.
 int qmm_internal_chain_flush(qmm_ctx * c);
-// the glue translation unit's copy of the IQ3 grids (qmm_device.hiph), on the current device.  Defined in qmm_ops.hip.
-int qmm_internal_ops_codebook(int off, const uint32_t * entries, int n);
+// the glue translation unit's copy of the codebook type's grid (qmm_device.hiph), on the current device.  Defined in qmm_ops.hip.
+int qmm_internal_ops_codebook(int type, const uint32_t * entries, int n);
 #define QMM_CHAIN_FLUSH(c)                                                      \
     do {                                                                        \
         if ((c)->chain_on) { int rc_ = qmm_internal_chain_flush(c); if (rc_) return rc_; } \
@@ -113,8 +113,8 @@ inline int fail(int code, const char * fmt, ...) {
         if (e_ != hipSuccess) return ::qmm::fail(QMM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// IQ3_XXS / IQ3_S before qmm_set_codebook: every launch is refused, nothing is computed
-inline int codebook_slot(int type) { return type == T_IQ3_S ? 1 : 0; }
+// IQ3_XXS / IQ3_S / IQ2_XS / IQ2_S before qmm_set_codebook: every launch is refused, nothing is computed
+inline int codebook_slot(int type) { return type == T_IQ3_S ? 1 : type == T_IQ2_XS ? 2 : type == T_IQ2_S ? 3 : 0; }
 inline int need_codebook(const qmm_ctx * c, int type, const char * who) {
     if (!type_codebook(type) || c->codebook[codebook_slot(type)]) return QMM_OK;
     return fail(QMM_EUNSUPPORTED, "%s: type %d needs its codebook first (qmm_set_codebook)", who, type);

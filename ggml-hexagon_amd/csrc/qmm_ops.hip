@@ -1100,8 +1100,8 @@ int run_glue(qmm_ctx * ctx, hipStream_t st, const GluePlan & p, const GlueArgs &
 } // namespace
 
 // qmm_set_codebook (qmm_api.hip) writes both code objects' tables: this one's serves get_rows_q_kernel
-int qmm_internal_ops_codebook(int off, const uint32_t * entries, int n) {
-    HIP_TRY(iq3_grid_upload(off, entries, n));
+int qmm_internal_ops_codebook(int type, const uint32_t * entries, int n) {
+    HIP_TRY(codebook_upload(type, entries, n));
     return QMM_OK;
 }
 

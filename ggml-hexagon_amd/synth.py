@@ -13,10 +13,11 @@ import numpy as np
 Q4_0, Q8_0, Q4_K, Q5_K, Q6_K = 2, 8, 12, 13, 14
 Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, IQ4_NL, IQ4_XS = 3, 6, 7, 10, 11, 20, 23      # ggml-common.h:174-207, 253-277, 405-418
 IQ3_XXS, IQ3_S = 18, 21                                                    # ggml-common.h:365-380
-BLCK = {Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q4_1: 32, Q5_0: 32, Q5_1: 32, Q2_K: 256, Q3_K: 256, IQ4_NL: 32, IQ4_XS: 256, IQ3_XXS: 256, IQ3_S: 256}
-TYPE_SIZE = {Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q2_K: 84, Q3_K: 110, IQ4_NL: 18, IQ4_XS: 136, IQ3_XXS: 98, IQ3_S: 110}
+IQ2_XS, IQ2_S = 17, 22                                                     # ggml-common.h:343-357
+BLCK = {Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q4_1: 32, Q5_0: 32, Q5_1: 32, Q2_K: 256, Q3_K: 256, IQ4_NL: 32, IQ4_XS: 256, IQ3_XXS: 256, IQ3_S: 256, IQ2_XS: 256, IQ2_S: 256}
+TYPE_SIZE = {Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q2_K: 84, Q3_K: 110, IQ4_NL: 18, IQ4_XS: 136, IQ3_XXS: 98, IQ3_S: 110, IQ2_XS: 74, IQ2_S: 82}
 NAMES = {Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K",
-         Q4_1: "q4_1", Q5_0: "q5_0", Q5_1: "q5_1", Q2_K: "q2_K", Q3_K: "q3_K", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", IQ3_XXS: "iq3_xxs", IQ3_S: "iq3_s"}
+         Q4_1: "q4_1", Q5_0: "q5_0", Q5_1: "q5_1", Q2_K: "q2_K", Q3_K: "q3_K", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", IQ3_XXS: "iq3_xxs", IQ3_S: "iq3_s", IQ2_XS: "iq2_xs", IQ2_S: "iq2_s"}
 BY_NAME = {v: k for k, v in NAMES.items()}
 BF16 = 30                 # no block format: rows of K bf16 values, K in multiples of 32 (the library's surface)
 
@@ -68,6 +69,11 @@ def synth_weights(t: int, rows: int, k: int, seed: int = 0, sigma: float = 0.02)
     elif t in (IQ3_XXS, IQ3_S):
         # every byte pattern is a valid block; w = d * (1 + 2 scale) * grid (IQ3_XXS: / 4), scale <= 15, whatever grid the caller's
         # codebook holds (<= 127): |d| log-uniform in [2^-10, 2^-4] keeps |w| < 2^-4 * 31 * 127 < 65504, the f16 prompt mode's range
+        d = np.exp2(rng.uniform(-10.0, -4.0, nb)).astype(np.float32) * rng.choice(np.array([-1.0, 1.0], np.float32), nb)
+        blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(nb, 2)
+    elif t in (IQ2_XS, IQ2_S):
+        # every byte pattern is a valid block; w = d * (0.5 + scale) * 0.25 * grid, scale <= 15, grid <= 43 in ggml's tables: the same
+        # |d| keeps |w| <= 166.6 |d| (and < 2^-4 * 3.875 * 127 for any table qmm_set_codebook takes), inside f16
         d = np.exp2(rng.uniform(-10.0, -4.0, nb)).astype(np.float32) * rng.choice(np.array([-1.0, 1.0], np.float32), nb)
         blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(nb, 2)
     else:
@@ -130,7 +136,7 @@ def synth_weights_torch(t: int, rows: int, k: int, device, seed: int = 0, sigma:
         blk[:, 82:84] = f16(3 * sigma / 10, signed=False)
     elif t == Q3_K:
         blk[:, 108:110] = f16(3 * sigma / 4 / 20)
-    elif t in (IQ3_XXS, IQ3_S):
+    elif t in (IQ3_XXS, IQ3_S, IQ2_XS, IQ2_S):
         d = torch.exp2(torch.rand(nb, device=device, generator=g) * 6.0 - 10.0) * (torch.randint(0, 2, (nb,), device=device, generator=g).float() * 2 - 1)
         blk[:, 0:2] = d.to(torch.float16).view(torch.uint8).reshape(nb, 2)
     else:

@@ -150,7 +150,10 @@ QMM_API int          qmm_event_synchronize(qmm_ctx * ctx, qmm_event * ev);      
  * (qmm_mul_mat*, qmm_mul_mat_id*, qmm_dequantize, QMM_OP_GET_ROWS) returns QMM_EUNSUPPORTED with "codebook" in qmm_last_error().
  * Both types: Q8_K activations; few tokens on matvec_kernel<type, n> (a group with other types runs as consecutive launches), prompt
  * batches on mfma_kernel<type, rows> in QMM_PREC_F16_Q8 and QMM_PREC_BF16; qmm_planar_type, qmm_q8_exact_supported and
- * qmm_mul_mat_group_norm_supported return 0; inside a chain recording they launch what was recorded and then themselves, directly. */
+ * qmm_mul_mat_group_norm_supported return 0; inside a chain recording they launch what was recorded and then themselves, directly.
+ * IQ2_XS = 17 and IQ2_S = 22 (ggml-common.h:343-357) go the same way in every respect (rows of K/256 * 74 and K/256 * 82 bytes).  Their
+ * grids hold eight magnitudes per entry: entry e is the two consecutive u32 2e (weights 0 .. 3) and 2e + 1 (weights 4 .. 7), and
+ * n_entries counts u32 words: 1024 for type 17 (512 entries), 2048 for type 22 (1024 entries). */
 QMM_API int          qmm_set_codebook(qmm_ctx * ctx, int type, const uint32_t * entries, int n_entries);
 
 /* bytes of one weight row of k values; 0 for a type that is no weight type or a k off its block size (BF16: 2 k, k a multiple of 32) */
