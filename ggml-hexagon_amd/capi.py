@@ -11,6 +11,7 @@ Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 2, 8, 12, 13, 14, 15
 Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, IQ4_NL, IQ4_XS = 3, 6, 7, 10, 11, 20, 23
 IQ3_XXS, IQ3_S = 18, 21  # need their grids first: Qmm.set_codebook
 IQ2_XS, IQ2_S = 17, 22   # likewise
+IQ1_S, IQ1_M = 19, 29    # likewise: one grid for both, set through either id
 BF16 = 30               # unquantized rows of K bf16 values (K % 32 == 0, rows on 16-byte boundaries): mul_mat, mul_mat_group, dequantize
 ACT_REF, ACT_X86 = 0, 1
 PREC_BF16, PREC_F16_Q8, PREC_Q8_EXACT = 0, 1, 2
@@ -208,8 +209,9 @@ class Qmm:
 
     def set_codebook(self, t, entries):
         """the grid of IQ3_XXS (256 entries) or IQ3_S (512): uint32 values, byte j of an entry = the magnitude of weight j; of IQ2_XS
-        (512 entries) or IQ2_S (1024): two uint32 per entry, weights 0..3 and 4..7 (1024 / 2048 values).  The library has none of its
-        own; derive it from ggml (tests/iq3_refs.py and tests/iq2_refs.py show how) and hand it to every context"""
+        (512 entries) or IQ2_S (1024): two uint32 per entry, weights 0..3 and 4..7 (1024 / 2048 values); of IQ1_S or IQ1_M (one grid of 2048 entries for
+        both, either id enables both): the same two uint32 per entry with int8 bytes -1 / 0 / +1 (4096 values).  The library has none of its
+        own; derive it from ggml (tests/iq3_refs.py, tests/iq2_refs.py and tests/iq1_refs.py show how) and hand it to every context"""
         import numpy as np
         e = np.ascontiguousarray(entries, dtype=np.uint32)
         self._chk(self.lib.qmm_set_codebook(self.ctx, t, e.ctypes.data, e.size))

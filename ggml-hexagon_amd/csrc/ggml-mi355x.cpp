@@ -52,7 +52,7 @@ mi355x_device_ctx      g_devs[GGML_MI355X_MAX_DEVICES];
 ggml_backend_device    g_devices[GGML_MI355X_MAX_DEVICES];
 int                    g_ndev = 0;
 
-// ----------------------------------------------------------------------------------------------- codebooks (IQ3_XXS, IQ3_S, IQ2_XS, IQ2_S)
+// ----------------------------------------------------------------------------------------------- codebooks (IQ3_XXS, IQ3_S, IQ2_XS, IQ2_S, IQ1_S / IQ1_M)
 
 // The grids of the two 3-bit i-quants are tables of ggml's source; this module carries none.  It reads them out of the ggml it is
 // loaded into, through the type's own to_float on blocks crafted so that every float IS one byte of one grid entry:
@@ -69,7 +69,38 @@ int                    g_ndev = 0;
 //           qh[ib] = 0x55 * (32 b >> 8): all four entries of a sub-block get the block's two high index bits.
 // The eight floats of entry i of block b are the bytes of entry e = 32 b + i: the words 2e (weights 0 .. 3) and 2e + 1 (4 .. 7).
 // Every four consecutive floats are one table word, byte j = float j.
+//
+// The two 1-bit i-quants index one grid of 2048 entries of eight values -1 / 0 / +1; it is read through IQ1_S's dequantizer
+//   IQ1_S   (50-byte block: f16 d | 32 index low bytes | 8 u16 of four 3-bit high index parts, a 3-bit scale and the delta sign): 64 blocks,
+//           d = 8.0, low byte (32 b + i) & 0xff, qh[ib] = h | h << 3 | h << 6 | h << 9 with h = 32 b >> 8, scale bits 0, delta +:
+// every float is 8 * (g + 0.125) = 8 g + 1, so the table is used only if every float is exactly -7, 1 or 9.  The words are IQ2's pair
+// form with int8 bytes (0xff, 0x00, 0x01); the kernel library enables IQ1_S and IQ1_M on it.
+static bool derive_iq1_grid(std::vector<uint32_t> & grid) {
+    const struct ggml_type_traits * tt = ggml_get_type_traits(GGML_TYPE_IQ1_S);
+    const size_t bs = 50, nblk = 64;
+    if (!tt || !tt->to_float || tt->blck_size != 256 || tt->type_size != bs) return false;
+    std::vector<uint8_t> blocks(nblk * bs, 0);
+    for (size_t b = 0; b < nblk; ++b) {
+        uint8_t * blk = blocks.data() + b * bs;
+        blk[0] = 0x00;  blk[1] = 0x48;                               // f16 8.0, little-endian
+        for (int i = 0; i < 32; ++i) blk[2 + i] = (uint8_t) ((32 * b + i) & 0xff);
+        const unsigned h = (unsigned) ((32 * b) >> 8), qh = h | h << 3 | h << 6 | h << 9;
+        for (int ib = 0; ib < 8; ++ib) { blk[34 + 2 * ib] = (uint8_t) (qh & 0xff);  blk[35 + 2 * ib] = (uint8_t) (qh >> 8); }
+    }
+    std::vector<float> out(nblk * 256);
+    tt->to_float(blocks.data(), out.data(), (int64_t) out.size());
+    grid.assign(nblk * 64, 0);
+    for (size_t w = 0; w < grid.size(); ++w)
+        for (int j = 0; j < 4; ++j) {
+            const float v = out[4 * w + j];
+            if (v != -7.0f && v != 1.0f && v != 9.0f) return false;
+            grid[w] |= (v == -7.0f ? 0xffu : v == 9.0f ? 0x01u : 0x00u) << (8 * j);
+        }
+    return true;
+}
+
 bool derive_codebook(enum ggml_type type, std::vector<uint32_t> & grid) {
+    if (type == GGML_TYPE_IQ1_S) return derive_iq1_grid(grid);
     const struct ggml_type_traits * tt = ggml_get_type_traits(type);
     const bool xxs = type == GGML_TYPE_IQ3_XXS, iq3 = xxs || type == GGML_TYPE_IQ3_S, xs = type == GGML_TYPE_IQ2_XS;
     const size_t bs = xxs ? 98 : iq3 ? 110 : xs ? 74 : 82, nblk = xxs ? 4 : iq3 ? 8 : xs ? 16 : 32;
@@ -102,10 +133,10 @@ bool derive_codebook(enum ggml_type type, std::vector<uint32_t> & grid) {
     return true;
 }
 
-// every device gets all four grids; a type counts as supported only if all of them took it
+// every device gets all five grids; a type counts as supported only if all of them took it (the last one serves IQ1_S and IQ1_M)
 void set_codebooks() {
-    const enum ggml_type types[4] = { GGML_TYPE_IQ3_XXS, GGML_TYPE_IQ3_S, GGML_TYPE_IQ2_XS, GGML_TYPE_IQ2_S };
-    for (int k = 0; k < 4; ++k) {
+    const enum ggml_type types[5] = { GGML_TYPE_IQ3_XXS, GGML_TYPE_IQ3_S, GGML_TYPE_IQ2_XS, GGML_TYPE_IQ2_S, GGML_TYPE_IQ1_S };
+    for (int k = 0; k < 5; ++k) {
         g_codebook_ok[k] = false;
         if (!qmm_set_codebook || g_ndev == 0) continue;              // a kernel library without the entry point: the types stay with the CPU
         std::vector<uint32_t> grid;

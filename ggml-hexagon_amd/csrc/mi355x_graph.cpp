@@ -6,16 +6,19 @@ namespace mi355x {
 
 // ----------------------------------------------------------------------------------------------- ops
 
-// IQ3_XXS / IQ3_S / IQ2_XS / IQ2_S: taken once every registered device holds the type's grid (ggml-mi355x.cpp derives it from ggml at registration and
+// IQ3_XXS / IQ3_S / IQ2_XS / IQ2_S / IQ1_S / IQ1_M: taken once every registered device holds the type's grid (ggml-mi355x.cpp derives it from ggml at registration and
 // hands it to qmm_set_codebook); a kernel library without that entry point, or a grid that does not pass the checks, leaves them to the CPU
-bool g_codebook_ok[4] = { false, false, false, false };
-static bool codebook_type(enum ggml_type t) { return t == GGML_TYPE_IQ3_XXS || t == GGML_TYPE_IQ3_S || t == GGML_TYPE_IQ2_XS || t == GGML_TYPE_IQ2_S; }
+bool g_codebook_ok[5] = { false, false, false, false, false };
+static bool codebook_type(enum ggml_type t) {
+    return t == GGML_TYPE_IQ3_XXS || t == GGML_TYPE_IQ3_S || t == GGML_TYPE_IQ2_XS || t == GGML_TYPE_IQ2_S || t == GGML_TYPE_IQ1_S || t == GGML_TYPE_IQ1_M;
+}
 
 bool type_supported(enum ggml_type t) {
     if (t == GGML_TYPE_IQ3_XXS) return g_codebook_ok[0];
     if (t == GGML_TYPE_IQ3_S)   return g_codebook_ok[1];
     if (t == GGML_TYPE_IQ2_XS)  return g_codebook_ok[2];
     if (t == GGML_TYPE_IQ2_S)   return g_codebook_ok[3];
+    if (t == GGML_TYPE_IQ1_S || t == GGML_TYPE_IQ1_M) return g_codebook_ok[4];             // one grid, both formats
     // the north-star's five formats plus SURVEY 8f-4's (round 2): any stock Q4_1 / Q5_0 / Q5_1 / Q2_K / Q3_K_* / IQ4_NL GGUF keeps its
     // matmul weights on the device; the kernel library answers the same question through qmm_row_size() != 0
     return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K ||

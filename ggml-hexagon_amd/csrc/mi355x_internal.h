@@ -230,7 +230,7 @@ void * hoist_elsewhere(mi355x_backend_ctx * ctx, const ggml_tensor * d);
 
 // ----------------------------------------------------------------------------------------------- mi355x_graph.cpp
 bool type_supported(enum ggml_type t);
-extern bool g_codebook_ok[4];                                        // IQ3_XXS, IQ3_S, IQ2_XS, IQ2_S: every device holds the grid (mi355x_graph.cpp)
+extern bool g_codebook_ok[5];                                        // IQ3_XXS, IQ3_S, IQ2_XS, IQ2_S, IQ1_S and IQ1_M: every device holds the grid (mi355x_graph.cpp)
 bool bf16_weight(const struct ggml_tensor * w);
 bool is_ours(const struct ggml_tensor * t);
 bool supports_mul_mat(const struct ggml_tensor * op);

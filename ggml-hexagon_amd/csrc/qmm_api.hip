@@ -78,6 +78,7 @@ static int check_mm(const qmm_ctx * c, int type, const void * w, int64_t rb, int
     if (const int rc = need_codebook(c, type, who)) return rc;
     if (K <= 0 || K % type_blck(type)) return fail(QMM_EUNSUPPORTED, "%s: K=%lld must be a multiple of %d", who, (long long) K, type_blck(type));
     if (rb < (int64_t) qmm_row_size(type, K)) return fail(QMM_EINVAL, "%s: weight row stride %lld < row size", who, (long long) rb);
+    if (iq1m_misaligned(type, w, rb)) return fail(QMM_EINVAL, "%s: IQ1_M rows must be 8-byte aligned (base address and row stride multiples of 8)", who);
     if ((uintptr_t) x % 16 || ldx % 4 || ldx < K) return fail(QMM_EINVAL, "%s: src1 must be 16-byte aligned with ldx %% 4 == 0", who);
     if (type_planar(type) && (!qmm_planar_type(type_base(type), K, rb) || (uintptr_t) w % 16))
         return fail(QMM_EINVAL, "%s: planar type %d wants 16-byte aligned rows and K a multiple of %d", who, type, type_base(type) == T_Q6_K ? 2048 : 256);
@@ -491,14 +492,16 @@ size_t qmm_row_size(int type, int64_t k) {
 int qmm_set_codebook(qmm_ctx * c, int type, const uint32_t * entries, int n_entries) {
     if (!c || !entries) return fail(QMM_EINVAL, "qmm_set_codebook: NULL context or table");
     if (!type_codebook(type))
-        return fail(QMM_EINVAL, "qmm_set_codebook: type %d takes no codebook (IQ2_XS = %d, IQ3_XXS = %d, IQ3_S = %d, IQ2_S = %d do)", type, T_IQ2_XS, T_IQ3_XXS, T_IQ3_S, T_IQ2_S);
-    // (n_entries counts 32-bit words: an IQ2 entry of eight magnitudes is two of them)
+        return fail(QMM_EINVAL, "qmm_set_codebook: type %d takes no codebook (IQ2_XS = %d, IQ3_XXS = %d, IQ1_S = %d, IQ3_S = %d, IQ2_S = %d, IQ1_M = %d do)", type, T_IQ2_XS, T_IQ3_XXS, T_IQ1_S, T_IQ3_S, T_IQ2_S, T_IQ1_M);
+    // (n_entries counts 32-bit words: an IQ2 or IQ1 entry of eight values is two of them)
     if (n_entries != type_codebook(type)) return fail(QMM_EINVAL, "qmm_set_codebook: type %d has %d entries, not %d", type, type_codebook(type), n_entries);
-    // the units hold a magnitude with its sign as an int8 (neg4, qmm_device.hiph)
+    // the units hold a magnitude with its sign as an int8 (neg4, qmm_device.hiph); IQ1's one table holds the int8 values themselves
     for (int i = 0; i < n_entries; ++i)
         for (int j = 0; j < 4; ++j) {
             const uint32_t v = (entries[i] >> (8 * j)) & 0xffu;
-            if (v < 1 || v > 127) return fail(QMM_EUNSUPPORTED, "qmm_set_codebook: entry %d holds %u; the kernels take magnitudes in 1 .. 127", i, v);
+            if (type_ternary(type)) {
+                if (v != 0xffu && v > 1) return fail(QMM_EUNSUPPORTED, "qmm_set_codebook: entry %d holds the byte 0x%02x; the IQ1 grid is -1, 0, +1 (0xff, 0x00, 0x01)", i / 2, v);
+            } else if (v < 1 || v > 127) return fail(QMM_EUNSUPPORTED, "qmm_set_codebook: entry %d holds %u; the kernels take magnitudes in 1 .. 127", i, v);
         }
     HIP_TRY(hipSetDevice(c->device));
     QMM_CHAIN_FLUSH(c);
@@ -523,6 +526,7 @@ int qmm_dequantize(qmm_ctx * c, int type, const void * w, int64_t rb, int64_t ro
     if (const int rc = need_codebook(c, type, "qmm_dequantize")) return rc;
     if (K <= 0 || K % type_blck(type)) return fail(QMM_EINVAL, "qmm_dequantize: K=%lld", (long long) K);
     if (rb < (int64_t) qmm_row_size(type, K)) return fail(QMM_EINVAL, "qmm_dequantize: row stride too small");
+    if (iq1m_misaligned(type, w, rb)) return fail(QMM_EINVAL, "qmm_dequantize: IQ1_M rows must be 8-byte aligned (base address and row stride multiples of 8)");
     if ((uintptr_t) dst % 16) return fail(QMM_EINVAL, "qmm_dequantize: dst must be 16-byte aligned");
     HIP_TRY(hipSetDevice(c->device));
     QMM_CHAIN_FLUSH(c);
@@ -716,6 +720,7 @@ static int check_mm_id(const qmm_ctx * c, const char * who, bool second, int typ
     const int rc = check_mm(c, type, as, rb, K, b, K, who);
     if (rc) return rc;
     if (b_nb1 % 16 || b_nb2 % 16 || ids_nb1 % 4 || d_nb1 % 4 || d_nb2 % 4 || expert_bytes % 2 || (ne11 != 1 && ne11 != n_used)) return fail(QMM_EINVAL, "%s: strides / ne11", who);
+    if (iq1m_misaligned(type, as, rb, expert_bytes)) return fail(QMM_EINVAL, "%s: IQ1_M experts must be 8-byte aligned (expert stride a multiple of 8)", who);
     return QMM_OK;
 }
 

@@ -120,7 +120,7 @@ inline bool sup_get_rows(const qmm_tensor * a, const qmm_tensor * ids, const qmm
     if (!a || !ids || !d || ids->type != G_I32 || d->type != G_F32 || !dense_rows(d) || nelements(d) == 0) return false;
     if (d->ne[0] != a->ne[0] || d->ne[1] != ids->ne[0] || d->ne[2] != ids->ne[1] || d->ne[3] != ids->ne[2] || ids->ne[3] != 1) return false;
     if (a->ne[2] != ids->ne[1] || a->ne[3] != ids->ne[2] || nrows(d) >= ((int64_t) 1 << 31)) return false;
-    if (type_known(a->type)) return a->ne[0] % type_blck(a->type) == 0 && a->nb[1] % 2 == 0;
+    if (type_known(a->type)) return a->ne[0] % type_blck(a->type) == 0 && a->nb[1] % 2 == 0 && !iq1m_misaligned(a->type, a->data, a->nb[1], a->nb[2] | a->nb[3]);
     return (a->type == G_F32 || a->type == G_F16) && dense_rows(a);
 }
 inline bool sup_mul_mat_f(const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * d) {

@@ -59,7 +59,7 @@ struct qmm_ctx {
     bool        chain_attr_set = false;      // the kernel's dynamic-LDS limit has been raised on this device
     int         chain_checked = 0;   // chain_launches when the error word was last read
     hipStream_t chain_stream = nullptr;         // stream of the recorded steps
-    bool        codebook[4] = { false, false, false, false };   // qmm_set_codebook: this context has the grid of IQ3_XXS / IQ3_S / IQ2_XS / IQ2_S (codebook_slot; until then the type is refused)
+    bool        codebook[5] = { false, false, false, false, false };   // qmm_set_codebook: this context has the grid of IQ3_XXS / IQ3_S / IQ2_XS / IQ2_S / IQ1_S and IQ1_M (codebook_slot; until then the type is refused)
     char        name[128] = {0};
     // qmm_trace_begin / qmm_trace_end: while set, every kernel launch of the MUL_MAT path, of the glue launches behind qmm_op_compute /
     // qmm_op_add_rms_norm (run_glue of qmm_ops.hip) and of the attention entry points (qmm_attn.hiph) appends its label here (host side only; bench.py buckets its roofline by the kernels a call actually
@@ -113,8 +113,9 @@ inline int fail(int code, const char * fmt, ...) {
         if (e_ != hipSuccess) return ::qmm::fail(QMM_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-// IQ3_XXS / IQ3_S / IQ2_XS / IQ2_S before qmm_set_codebook: every launch is refused, nothing is computed
-inline int codebook_slot(int type) { return type == T_IQ3_S ? 1 : type == T_IQ2_XS ? 2 : type == T_IQ2_S ? 3 : 0; }
+// IQ3_XXS / IQ3_S / IQ2_XS / IQ2_S / IQ1_S / IQ1_M before qmm_set_codebook: every launch is refused, nothing is computed
+// (IQ1_S and IQ1_M index one grid: one slot, set through either id)
+inline int codebook_slot(int type) { return type == T_IQ3_S ? 1 : type == T_IQ2_XS ? 2 : type == T_IQ2_S ? 3 : type_ternary(type) ? 4 : 0; }
 inline int need_codebook(const qmm_ctx * c, int type, const char * who) {
     if (!type_codebook(type) || c->codebook[codebook_slot(type)]) return QMM_OK;
     return fail(QMM_EUNSUPPORTED, "%s: type %d needs its codebook first (qmm_set_codebook)", who, type);

@@ -14,10 +14,11 @@ Q4_0, Q8_0, Q4_K, Q5_K, Q6_K = 2, 8, 12, 13, 14
 Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, IQ4_NL, IQ4_XS = 3, 6, 7, 10, 11, 20, 23      # ggml-common.h:174-207, 253-277, 405-418
 IQ3_XXS, IQ3_S = 18, 21                                                    # ggml-common.h:365-380
 IQ2_XS, IQ2_S = 17, 22                                                     # ggml-common.h:343-357
-BLCK = {Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q4_1: 32, Q5_0: 32, Q5_1: 32, Q2_K: 256, Q3_K: 256, IQ4_NL: 32, IQ4_XS: 256, IQ3_XXS: 256, IQ3_S: 256, IQ2_XS: 256, IQ2_S: 256}
-TYPE_SIZE = {Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q2_K: 84, Q3_K: 110, IQ4_NL: 18, IQ4_XS: 136, IQ3_XXS: 98, IQ3_S: 110, IQ2_XS: 74, IQ2_S: 82}
+IQ1_S, IQ1_M = 19, 29                                                      # ggml-common.h:382-402
+BLCK = {Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q4_1: 32, Q5_0: 32, Q5_1: 32, Q2_K: 256, Q3_K: 256, IQ4_NL: 32, IQ4_XS: 256, IQ3_XXS: 256, IQ3_S: 256, IQ2_XS: 256, IQ2_S: 256, IQ1_S: 256, IQ1_M: 256}
+TYPE_SIZE = {Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q2_K: 84, Q3_K: 110, IQ4_NL: 18, IQ4_XS: 136, IQ3_XXS: 98, IQ3_S: 110, IQ2_XS: 74, IQ2_S: 82, IQ1_S: 50, IQ1_M: 56}
 NAMES = {Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K",
-         Q4_1: "q4_1", Q5_0: "q5_0", Q5_1: "q5_1", Q2_K: "q2_K", Q3_K: "q3_K", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", IQ3_XXS: "iq3_xxs", IQ3_S: "iq3_s", IQ2_XS: "iq2_xs", IQ2_S: "iq2_s"}
+         Q4_1: "q4_1", Q5_0: "q5_0", Q5_1: "q5_1", Q2_K: "q2_K", Q3_K: "q3_K", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", IQ3_XXS: "iq3_xxs", IQ3_S: "iq3_s", IQ2_XS: "iq2_xs", IQ2_S: "iq2_s", IQ1_S: "iq1_s", IQ1_M: "iq1_m"}
 BY_NAME = {v: k for k, v in NAMES.items()}
 BF16 = 30                 # no block format: rows of K bf16 values, K in multiples of 32 (the library's surface)
 
@@ -76,6 +77,17 @@ def synth_weights(t: int, rows: int, k: int, seed: int = 0, sigma: float = 0.02)
         # |d| keeps |w| <= 166.6 |d| (and < 2^-4 * 3.875 * 127 for any table qmm_set_codebook takes), inside f16
         d = np.exp2(rng.uniform(-10.0, -4.0, nb)).astype(np.float32) * rng.choice(np.array([-1.0, 1.0], np.float32), nb)
         blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(nb, 2)
+    elif t in (IQ1_S, IQ1_M):
+        # every byte pattern is a valid block but for the f16 scale; w = d * (2 scale + 1) * (grid +- 0.125), scale <= 7, grid in
+        # -1 .. 1: the same |d| keeps |w| <= 16.875 |d|.  IQ1_S has d in front; IQ1_M spreads its f16 over the top nibbles of the
+        # four scale words (bytes 49, 51, 53, 55), lowest nibble first
+        d = np.exp2(rng.uniform(-10.0, -4.0, nb)).astype(np.float32) * rng.choice(np.array([-1.0, 1.0], np.float32), nb)
+        if t == IQ1_S:
+            blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(nb, 2)
+        else:
+            h = d.astype(np.float16).view(np.uint16).astype(np.uint32)
+            for j in range(4):
+                blk[:, 49 + 2 * j] = (blk[:, 49 + 2 * j] & 0x0f) | (((h >> (4 * j)) & 15) << 4).astype(np.uint8)
     else:
         raise ValueError(t)
     return blk.reshape(rows, -1)
@@ -139,6 +151,15 @@ def synth_weights_torch(t: int, rows: int, k: int, device, seed: int = 0, sigma:
     elif t in (IQ3_XXS, IQ3_S, IQ2_XS, IQ2_S):
         d = torch.exp2(torch.rand(nb, device=device, generator=g) * 6.0 - 10.0) * (torch.randint(0, 2, (nb,), device=device, generator=g).float() * 2 - 1)
         blk[:, 0:2] = d.to(torch.float16).view(torch.uint8).reshape(nb, 2)
+    elif t in (IQ1_S, IQ1_M):
+        d = torch.exp2(torch.rand(nb, device=device, generator=g) * 6.0 - 10.0) * (torch.randint(0, 2, (nb,), device=device, generator=g).float() * 2 - 1)
+        hb = d.to(torch.float16).view(torch.uint8).reshape(nb, 2)
+        if t == IQ1_S:
+            blk[:, 0:2] = hb
+        else:
+            for j in range(4):
+                nib = (hb[:, j // 2] >> (4 * (j % 2))) & 15
+                blk[:, 49 + 2 * j] = (blk[:, 49 + 2 * j] & 0x0f) | (nib << 4)
     else:
         raise ValueError(t)
     return blk.reshape(rows, -1)

@@ -153,7 +153,13 @@ QMM_API int          qmm_event_synchronize(qmm_ctx * ctx, qmm_event * ev);      
  * qmm_mul_mat_group_norm_supported return 0; inside a chain recording they launch what was recorded and then themselves, directly.
  * IQ2_XS = 17 and IQ2_S = 22 (ggml-common.h:343-357) go the same way in every respect (rows of K/256 * 74 and K/256 * 82 bytes).  Their
  * grids hold eight magnitudes per entry: entry e is the two consecutive u32 2e (weights 0 .. 3) and 2e + 1 (weights 4 .. 7), and
- * n_entries counts u32 words: 1024 for type 17 (512 entries), 2048 for type 22 (1024 entries). */
+ * n_entries counts u32 words: 1024 for type 17 (512 entries), 2048 for type 22 (1024 entries).
+ * IQ1_S = 19 and IQ1_M = 29 (ggml-common.h:382-402; rows of K/256 * 50 and K/256 * 56 bytes) index ONE grid of 2048 entries of eight
+ * values -1 / 0 / +1.  It comes in the same word-pair form with every byte an int8 (0xff, 0x00 or 0x01; anything else is
+ * QMM_EUNSUPPORTED with "-1, 0, +1" in the message), n_entries = 4096 words.  The two ids name one table: a successful call with either
+ * enables both types on the context, and until then both are refused as above.  The same paths as IQ2.  IQ1_M rows must start on 8-byte
+ * boundaries (base address, row stride and expert stride multiples of 8, as ggml's block_iq1_m is aligned; QMM_EINVAL with "8-byte"
+ * otherwise, and QMM_OP_GET_ROWS answers not supported); IQ1_S rows on 2-byte ones, as every 2-byte-aligned block format. */
 QMM_API int          qmm_set_codebook(qmm_ctx * ctx, int type, const uint32_t * entries, int n_entries);
 
 /* bytes of one weight row of k values; 0 for a type that is no weight type or a k off its block size (BF16: 2 k, k a multiple of 32) */
