@@ -12,6 +12,7 @@ Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, IQ4_NL, IQ4_XS = 3, 6, 7, 10, 11, 20, 23
 IQ3_XXS, IQ3_S = 18, 21  # need their grids first: Qmm.set_codebook
 IQ2_XS, IQ2_S = 17, 22   # likewise
 IQ1_S, IQ1_M = 19, 29    # likewise: one grid for both, set through either id
+TQ1_0, TQ2_0 = 34, 35    # the ternary formats: no grid, nothing to set
 BF16 = 30               # unquantized rows of K bf16 values (K % 32 == 0, rows on 16-byte boundaries): mul_mat, mul_mat_group, dequantize
 ACT_REF, ACT_X86 = 0, 1
 PREC_BF16, PREC_F16_Q8, PREC_Q8_EXACT = 0, 1, 2

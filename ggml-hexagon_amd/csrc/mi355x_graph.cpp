@@ -23,7 +23,8 @@ bool type_supported(enum ggml_type t) {
     // matmul weights on the device; the kernel library answers the same question through qmm_row_size() != 0
     return t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q5_K || t == GGML_TYPE_Q6_K ||
            t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1 || t == GGML_TYPE_Q2_K || t == GGML_TYPE_Q3_K || t == GGML_TYPE_IQ4_NL || t == GGML_TYPE_IQ4_XS ||
-           t == GGML_TYPE_BF16;           // unquantized checkpoints: MUL_MAT only (supports_mul_mat_id refuses it), and no fold takes it (bf16_weight)
+           t == GGML_TYPE_TQ1_0 || t == GGML_TYPE_TQ2_0 ||      // the ternary file types: no grid, taken unconditionally
+           t == GGML_TYPE_BF16;          // unquantized checkpoints: MUL_MAT only (supports_mul_mat_id refuses it), and no fold takes it (bf16_weight)
 }
 
 // A BF16 weight: the library runs it through kernels of their own (rows of K bf16 values, K in multiples of 32, rows on 16-byte

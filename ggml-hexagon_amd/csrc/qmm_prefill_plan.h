@@ -71,7 +71,7 @@ inline bool mfma_regb_supports(const PrefillRules & r, int type) {
                                          type == T_Q4_1 || type == T_Q5_0 || type == T_Q5_1 || type == T_IQ4_NL || type == T_IQ4_XS || ((type == T_Q2_K || type == T_Q3_K) && r.regb_q23));
 }
 // K elements per LDS stage of a type's kernels (MfmaBK, Regb<T>::BK)
-constexpr int mfma_bk(int type) { return type_base(type) == T_Q6_K || type_base(type) == T_Q2_K || type_base(type) == T_Q3_K ? 128 : 64; }
+constexpr int mfma_bk(int type) { return type_base(type) == T_Q6_K || type_base(type) == T_Q2_K || type_base(type) == T_Q3_K || type_base(type) == T_TQ2_0 ? 128 : 64; }
 
 // k-order of the 16-bit operand (PERM of the prep kernels) from the weight type: the register-B lane orders (qmm_mfma_regb.hiph)
 inline int prefill_perm(const PrefillRules & r, int type) {

@@ -15,10 +15,11 @@ Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, IQ4_NL, IQ4_XS = 3, 6, 7, 10, 11, 20, 23      # gg
 IQ3_XXS, IQ3_S = 18, 21                                                    # ggml-common.h:365-380
 IQ2_XS, IQ2_S = 17, 22                                                     # ggml-common.h:343-357
 IQ1_S, IQ1_M = 19, 29                                                      # ggml-common.h:382-402
-BLCK = {Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q4_1: 32, Q5_0: 32, Q5_1: 32, Q2_K: 256, Q3_K: 256, IQ4_NL: 32, IQ4_XS: 256, IQ3_XXS: 256, IQ3_S: 256, IQ2_XS: 256, IQ2_S: 256, IQ1_S: 256, IQ1_M: 256}
-TYPE_SIZE = {Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q2_K: 84, Q3_K: 110, IQ4_NL: 18, IQ4_XS: 136, IQ3_XXS: 98, IQ3_S: 110, IQ2_XS: 74, IQ2_S: 82, IQ1_S: 50, IQ1_M: 56}
+TQ1_0, TQ2_0 = 34, 35                                                      # ggml-common.h:233-246
+BLCK = {Q4_0: 32, Q8_0: 32, Q4_K: 256, Q5_K: 256, Q6_K: 256, Q4_1: 32, Q5_0: 32, Q5_1: 32, Q2_K: 256, Q3_K: 256, IQ4_NL: 32, IQ4_XS: 256, IQ3_XXS: 256, IQ3_S: 256, IQ2_XS: 256, IQ2_S: 256, IQ1_S: 256, IQ1_M: 256, TQ1_0: 256, TQ2_0: 256}
+TYPE_SIZE = {Q4_0: 18, Q8_0: 34, Q4_K: 144, Q5_K: 176, Q6_K: 210, Q4_1: 20, Q5_0: 22, Q5_1: 24, Q2_K: 84, Q3_K: 110, IQ4_NL: 18, IQ4_XS: 136, IQ3_XXS: 98, IQ3_S: 110, IQ2_XS: 74, IQ2_S: 82, IQ1_S: 50, IQ1_M: 56, TQ1_0: 54, TQ2_0: 66}
 NAMES = {Q4_0: "q4_0", Q8_0: "q8_0", Q4_K: "q4_K", Q5_K: "q5_K", Q6_K: "q6_K",
-         Q4_1: "q4_1", Q5_0: "q5_0", Q5_1: "q5_1", Q2_K: "q2_K", Q3_K: "q3_K", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", IQ3_XXS: "iq3_xxs", IQ3_S: "iq3_s", IQ2_XS: "iq2_xs", IQ2_S: "iq2_s", IQ1_S: "iq1_s", IQ1_M: "iq1_m"}
+         Q4_1: "q4_1", Q5_0: "q5_0", Q5_1: "q5_1", Q2_K: "q2_K", Q3_K: "q3_K", IQ4_NL: "iq4_nl", IQ4_XS: "iq4_xs", IQ3_XXS: "iq3_xxs", IQ3_S: "iq3_s", IQ2_XS: "iq2_xs", IQ2_S: "iq2_s", IQ1_S: "iq1_s", IQ1_M: "iq1_m", TQ1_0: "tq1_0", TQ2_0: "tq2_0"}
 BY_NAME = {v: k for k, v in NAMES.items()}
 BF16 = 30                 # no block format: rows of K bf16 values, K in multiples of 32 (the library's surface)
 
@@ -88,6 +89,10 @@ def synth_weights(t: int, rows: int, k: int, seed: int = 0, sigma: float = 0.02)
             h = d.astype(np.float16).view(np.uint16).astype(np.uint32)
             for j in range(4):
                 blk[:, 49 + 2 * j] = (blk[:, 49 + 2 * j] & 0x0f) | (((h >> (4 * j)) & 15) << 4).astype(np.uint8)
+    elif t in (TQ1_0, TQ2_0):
+        # every byte value is valid content (a TQ1_0 byte above 242 and TQ2_0's code 3 included); w = d * (trit - 1), or d * (code - 1)
+        # in -1 .. 2: d is the LAST field of the block and of the model's own magnitude
+        blk[:, -2:] = _f16_bytes(rng, nb, sigma)
     else:
         raise ValueError(t)
     return blk.reshape(rows, -1)
@@ -160,6 +165,8 @@ def synth_weights_torch(t: int, rows: int, k: int, device, seed: int = 0, sigma:
             for j in range(4):
                 nib = (hb[:, j // 2] >> (4 * (j % 2))) & 15
                 blk[:, 49 + 2 * j] = (blk[:, 49 + 2 * j] & 0x0f) | (nib << 4)
+    elif t in (TQ1_0, TQ2_0):
+        blk[:, -2:] = f16(sigma)
     else:
         raise ValueError(t)
     return blk.reshape(rows, -1)

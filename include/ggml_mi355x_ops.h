@@ -24,7 +24,7 @@ extern "C" {
 
 typedef struct qmm_tensor {
     void *  data;             /* DEVICE pointer */
-    int32_t type;             /* ggml_type: F32 = 0, F16 = 1, I32 = 26, quantized types as in ggml_mi355x_qmm.h */
+    int32_t type;             /* ggml_type: F32 = 0, F16 = 1, I32 = 26, quantized types as in ggml_mi355x_qmm.h (TQ1_0 = 34, TQ2_0 = 35 among them) */
     int32_t flags;            /* 0, or QMM_TENSOR_* bits where an entry point names one */
     int64_t ne[4];            /* elements */
     int64_t nb[4];            /* bytes */

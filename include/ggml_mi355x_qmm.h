@@ -27,6 +27,8 @@
  *     Calls are asynchronous on that stream; nothing synchronizes except qmm_synchronize / qmm_memcpy_h2d/_d2h;
  *   - `type` is ggml's enum ggml_type value: Q4_0=2, Q8_0=8, Q4_K=12, Q5_K=13, Q6_K=14 (the north-star's five) and, SURVEY 8f-4,
  *     Q4_1=3, Q5_0=6, Q5_1=7, Q2_K=10, Q3_K=11, IQ4_NL=20 (ggml/src/ggml-common.h:174-207, 253-277, 405-410);
+ *     IQ4_XS=23, IQ3_XXS=18, IQ3_S=21, IQ2_XS=17, IQ2_S=22, IQ1_S=19, IQ1_M=29 (the last six: qmm_set_codebook first),
+ *     TQ1_0=34, TQ2_0=35 (ggml-common.h:233-246; below: "Ternary weights");
  *     BF16=30 for qmm_mul_mat, qmm_mul_mat_group[_ex], qmm_row_size and qmm_dequantize only (below: "BF16 weights");
  *   - weights are in GGUF wire layout: rows of blocks, `w_row_bytes` apart (>= K/blck*type_size);
  *   - returns 0 on success, a negative QMM_E* code otherwise (qmm_last_error() has the text, per thread).
@@ -35,6 +37,14 @@
  *     calls from one thread and on one stream at a time.  The workspace grows on demand, which synchronizes the
  *     device: run a shape once before capturing it into a hipGraph.  Several contexts per device are fine (the
  *     plugin's logical devices each have their own).
+ *
+ * Ternary weights (TQ1_0 = 34: rows of K/256 * 54 bytes, five trits per byte; TQ2_0 = 35: K/256 * 66 bytes, two bits per weight): no
+ *   table and no call ahead of the first launch.  Blocks on 2-byte boundaries.  Every byte value is valid content and is decoded as
+ *   ggml's dequantize_row_tq1_0 / _tq2_0 do (a TQ1_0 byte above 242 by the same multiply; TQ2_0's code 3 is +2).  Q8_K activations; the
+ *   paths of IQ1_S / IQ1_M: matvec_kernel<type, n> for 1 .. 8 tokens with the folds of qmm_mul_mat_group_ex, the MUL_MAT_ID entry
+ *   points, mfma_kernel<type, rows> for prompt batches in QMM_PREC_F16_Q8 and QMM_PREC_BF16 (QMM_PREC_Q8_EXACT runs them as
+ *   QMM_PREC_F16_Q8), qmm_dequantize, QMM_OP_GET_ROWS, qmm_row_size; qmm_planar_type and qmm_q8_exact_supported return 0.  In
+ *   QMM_PREC_F16_Q8 a TQ2_0 block with code 3 and |d| > 32752 exceeds f16: qmm_synchronize reports "non-finite", QMM_PREC_BF16 computes it.
  *
  * BF16 weights (type 30): rows of K bf16 values (w_row_bytes >= 2 K), the base address and the row stride multiples of 16 bytes, K a
  *   multiple of 32, M >= 1, N >= 1, ldx >= K and ldd >= M with the alignment rules of the quantized types on x; anything else is refused
