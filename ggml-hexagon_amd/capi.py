@@ -199,7 +199,8 @@ class Qmm:
         self._chk(self.lib.qmm_set_precision(self.ctx, p))
 
     def q8_exact_supported(self, t, k):
-        """1 when a prefill mul_mat of this weight type and K is exact in PREC_Q8_EXACT, 0 when that mode runs it as PREC_F16_Q8"""
+        """1 when a prefill mul_mat of this weight type and K is exact in PREC_Q8_EXACT (Q2_K, Q3_K, Q4_K, Q5_K, Q6_K and IQ4_XS at
+        K % 256 == 0), 0 when that mode runs it as PREC_F16_Q8"""
         return self.lib.qmm_q8_exact_supported(t, k)
 
     def synchronize(self):

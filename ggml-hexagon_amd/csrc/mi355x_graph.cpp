@@ -375,8 +375,8 @@ enum ggml_status graph_compute_once(ggml_backend_t backend, struct ggml_cgraph *
 // reference's own bar), and the device stays in that mode: a model with such a block needs it for every prompt.  Re-issuing is safe:
 // a graph's leaves and inputs are never reused by ggml-alloc, every other tensor is rewritten by its node, KV-cache stores rewrite the
 // same rows with the same values.
-// With GGML_MI355X_PREC=q8 (sw().prec_q8) the library's context is in QMM_PREC_Q8_EXACT (qmm_create reads the same switch): Q4_K / Q5_K /
-// Q6_K prompts dot integers and cannot overflow, so only a weight type that mode runs as f16 on Q8 activations can bring a graph here;
+// With GGML_MI355X_PREC=q8 (sw().prec_q8) the library's context is in QMM_PREC_Q8_EXACT (qmm_create reads the same switch): Q2_K / Q3_K /
+// Q4_K / Q5_K / Q6_K / IQ4_XS prompts dot integers and cannot overflow, so only a weight type that mode runs as f16 on Q8 activations can bring a graph here;
 // the retry then moves the device from q8 to bf16, for every type.
 enum ggml_status backend_graph_compute(ggml_backend_t backend, struct ggml_cgraph * cgraph) {
     bool overflow = false;

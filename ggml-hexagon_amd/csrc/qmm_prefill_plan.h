@@ -85,15 +85,18 @@ inline int prefill_perm(const PrefillRules & r, int type) {
 }
 
 // QMM_PREC_Q8_EXACT covers the K-quant formats whose sub-block scale is an integer that can go into the weight before the int8 MFMA
-// (wire layout; planar Q6_K rows, every other type and MUL_MAT_ID run as in QMM_PREC_F16_Q8)
-inline bool q8x_supports(int type, int64_t K) { return (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K) && K > 0 && K % 256 == 0; }
+// (wire layout; planar Q6_K rows, every other type and MUL_MAT_ID run as in QMM_PREC_F16_Q8): the five K-quants and IQ4_XS, i.e. every
+// type with a Q8xBlock (qmm_mfma_q8x.hiph)
+inline bool q8x_supports(int type, int64_t K) {
+    return (type == T_Q4_K || type == T_Q5_K || type == T_Q6_K || type == T_Q2_K || type == T_Q3_K || type == T_IQ4_XS) && K > 0 && K % 256 == 0;
+}
 // ... and the rules such a call, or any call of another mode, is planned by
 inline PrefillRules prefill_effective_rules(PrefillRules r, int type, int64_t K, bool gather) {
     if (r.prec == QMM_PREC_Q8_EXACT && (gather || !q8x_supports(type, K))) r.prec = QMM_PREC_F16_Q8;
     return r;
 }
 constexpr int Q8X_ROWS = 128, Q8X_TOKENS = 64;      // tile of a workgroup of mfma_q8x_kernel: 4 waves of 32 rows each on the same 64 tokens
-constexpr int Q8X_KEY  = 1;                         // one operand for the three formats (the other modes' keys are 0 or >= 6)
+constexpr int Q8X_KEY  = 1;                         // one operand for all its formats (the other modes' keys are 0 or >= 6)
 
 namespace plan_detail {
 

@@ -16,7 +16,7 @@
 // X(NAME, kind, default, text); [lib] = read by the kernel library on every qmm_create (or once per process: ATTN_*, RCCL_LIB),
 // [plugin] = read once by the ggml backend module at its first use
 #define QMM_SWITCHES(X)                                                                                                              \
-    X(PREC,                 STR,     0, "[lib+plugin] prefill numerics: bf16 (or 0) = bf16, q8 (or 2) = Q8-exact int8 MFMA for Q4_K / Q5_K / Q6_K, anything else = f16 on Q8 activations (the default)") \
+    X(PREC,                 STR,     0, "[lib+plugin] prefill numerics: bf16 (or 0) = bf16, q8 (or 2) = Q8-exact int8 MFMA for Q2_K .. Q6_K and IQ4_XS, anything else = f16 on Q8 activations (the default)") \
     X(ACT_MODE,             ATOI,    0, "[lib] Q8_0 activation rounding: 0 = quantize_row_q8_0_ref form, non-zero = x86 AVX2 form") \
     X(SPLITK,               ATOI,    1, "[lib] split K over workgroups when a prefill MUL_MAT has too few tiles; 0 = off, n > 1 caps the factor") \
     X(SPLITK_COMBINE,       ATOI,    0, "[lib] 1 = split-K ranges combined inside the launch instead of by a reduce kernel (measured a wash)") \

@@ -91,10 +91,11 @@ enum { QMM_ACT_REF = 0, QMM_ACT_X86 = 1 };
 enum {
     QMM_PREC_BF16 = 0,     /* dequantized weights and activations rounded to bf16, f32 MFMA accumulate   */
     QMM_PREC_F16_Q8 = 1,   /* activations Q8-quantized as the CPU backend does, then f16 MFMA (default)  */
-    /* Q8-exact (opt-in): for Q4_K, Q5_K and Q6_K weights in wire layout the kernel forms, per 256-element superblock, the integers
-     * of ggml_vec_dot_q{4,5,6}_K_q8_K (sumi = sum_j sc_j * (q_j . q8_j) and, for Q4_K / Q5_K, summs = sum_j m_j * bsum_j) on the
-     * int8 MFMA, converts them to f32 once per superblock (d_w * d_a * sumi - dmin_w * d_a * summs) and accumulates in f32: only
-     * the f32 order of the superblock terms differs from the CPU backend; no operand is rounded to 16 bits, so no weight block is out
+    /* Q8-exact (opt-in): for the six formats Q2_K, Q3_K, Q4_K, Q5_K, Q6_K and IQ4_XS in wire layout the kernel forms, per 256-element
+     * superblock, the integers of ggml_vec_dot_{q2_K,q3_K,q4_K,q5_K,q6_K,iq4_xs}_q8_K (sumi = sum_j sc_j * (q_j . q8_j) and, for Q2_K /
+     * Q4_K / Q5_K, summs = sum_j m_j * bsum_j) on the int8 MFMA, converts them to f32 once per superblock (d_w * d_a * sumi - dmin_w *
+     * d_a * summs) and accumulates in f32: only the f32 order of the superblock terms differs from the CPU backend (Q3_K: from its eight
+     * f32 lanes; IQ4_XS: from its one f32 term per 32-weight sub-block); no operand is rounded to 16 bits, so no weight block is out
      * of range.  Fallback: a call with qmm_q8_exact_supported(type, K) == 0 (every other weight type, planar rows) and every
      * prefill-size qmm_mul_mat_id* run the QMM_PREC_F16_Q8 path, bit-identical to the default mode (qmm_trace_* shows which ran).
      * qmm_mul_mat_swiglu_in and the fused norm of qmm_mul_mat_group_ex remain default-mode only. */
@@ -115,7 +116,7 @@ QMM_API int          qmm_device_info(const qmm_ctx * ctx, char * name, size_t na
 QMM_API int          qmm_set_act_mode(qmm_ctx * ctx, int act_mode);
 QMM_API int          qmm_set_precision(qmm_ctx * ctx, int prec);
 /* 1 when a prefill (N > QMM_MATVEC_MAX_N) qmm_mul_mat / qmm_mul_mat_group of this weight type and K is computed exactly in
- * QMM_PREC_Q8_EXACT, 0 when that mode runs it as QMM_PREC_F16_Q8 */
+ * QMM_PREC_Q8_EXACT (types 10, 11, 12, 13, 14 and 23 at K % 256 == 0), 0 when that mode runs it as QMM_PREC_F16_Q8 */
 QMM_API int          qmm_q8_exact_supported(int type, int64_t K);
 
 QMM_API void *       qmm_malloc(qmm_ctx * ctx, size_t bytes);
