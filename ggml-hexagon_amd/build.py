@@ -30,21 +30,23 @@ def _newer(target: Path, sources) -> bool:
 
 def build_qmm(force: bool = False) -> Path:
     """the kernel library behind include/ggml_mi355x_qmm.h and include/ggml_mi355x_ops.h: one object per translation unit
-    (qmm_api.hip = the quantized MUL_MAT path with, as its section qmm_prefill.hiph, the prompt-batch launches, qmm_ops.hip = the glue ops (what they launch: qmm_glue_plan.h) and, as its section qmm_attn.hiph (with qmm_attn_rows.hiph), the attention launches, qmm_comm.hip = the RCCL exchange of a one-process row split), rebuilt only when its sources changed"""
+    (qmm_api.hip = the quantized MUL_MAT path with, as its section qmm_prefill.hiph, the prompt-batch launches, qmm_matvec.hip = the few-token mat-vec kernels, the one unit compiled with kernel-argument preload, qmm_ops.hip = the glue ops (what they launch: qmm_glue_plan.h) and, as its section qmm_attn.hiph (with qmm_attn_rows.hiph), the attention launches, qmm_comm.hip = the RCCL exchange of a one-process row split), rebuilt only when its sources changed"""
     headers = sorted(CSRC.glob("qmm_*.hiph")) + sorted(CSRC.glob("qmm_*.h")) + sorted((ROOT / "include").glob("ggml_mi355x_*.h"))
-    units = [CSRC / "qmm_api.hip", CSRC / "qmm_ops.hip", CSRC / "qmm_comm.hip"]
+    units = [CSRC / "qmm_api.hip", CSRC / "qmm_matvec.hip", CSRC / "qmm_ops.hip", CSRC / "qmm_comm.hip"]
     if not force and _newer(QMM_SO, units + headers):
         return QMM_SO
     if not shutil.which(HIPCC):
         # a library older than its sources is never used silently: a stale kernel must not be tested or benchmarked
         raise RuntimeError("hipcc not found and libggml_mi355x_qmm.so is " + ("older than its sources" if QMM_SO.exists() else "missing"))
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fno-slp-vectorize"]
+    # the leading scalar parameters of the mat-vec kernels arrive in SGPRs (csrc/qmm_matvec.hip); the flag moves every kernel of a unit
+    unit_flags = {"qmm_matvec.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=8"]}
     objs, jobs = [], []
     for u in units:
         obj = CSRC / (u.stem + ".o")
         objs.append(obj)
         if force or not _newer(obj, [u] + headers):
-            jobs.append(subprocess.Popen([HIPCC, *flags, "-c", str(u), "-o", str(obj)]))
+            jobs.append(subprocess.Popen([HIPCC, *flags, *unit_flags.get(u.name, []), "-c", str(u), "-o", str(obj)]))
     for j in jobs:
         if j.wait() != 0:
             raise subprocess.CalledProcessError(j.returncode, j.args)

@@ -28,31 +28,15 @@ static_assert(QMM_MATVEC_MAX_N == 8, "QMM_FOR_NTOK lists the token counts");
 
 static MatvecRules matvec_rules(const qmm_ctx * c) { return { c->cus, c->mv_bpc, c->mv_kmix, c->mv_onepass, c->act_mode }; }
 
-using MatvecKernel = void (*)(MatvecGroup, const float *, int64_t, int, int, int);
-
-// the plan's instantiation for NT tokens (with Q8_0 matrices in a mixed group the kernel exists for NT <= 4 only, no fused norm: matvec_group_plan)
-template <int NT> static MatvecKernel matvec_instance(const MatvecLaunch & l) {
-    if constexpr (NT <= 4) {
-        if (l.kind == MV_MIXED_Q80) return l.ex ? matvec_kmix_kernel<NT, true, true> : matvec_kmix_kernel<NT, false, true>;
-    }
-    if (l.kind != MV_PER_TYPE) return l.ex ? matvec_kmix_kernel<NT, true> : matvec_kmix_kernel<NT, false>;
-#define QMM_X(TT) return l.ex ? matvec_kernel<TT, NT, true> : matvec_kernel<TT, NT, false>
-    QMM_FOR_TYPE(l.type, QMM_X)
-#undef QMM_X
-}
-
 // the executor of every few-token launch (group calls and chain steps that go out on their own): the plan's instantiation on g
 static int run_matvec(qmm_ctx * c, hipStream_t st, const MatvecLaunch & l, const MatvecGroup & g, const float * x, int64_t ldx) {
     char text[96];
     if (l.error) { l.text(text, sizeof(text)); return fail(l.error, "%s", text); }
-    MatvecKernel kern = nullptr;
-#define QMM_X(NT) kern = matvec_instance<NT>(l); break
-    QMM_FOR_NTOK(l.ntok, QMM_X)
-#undef QMM_X
+    const MatvecKernel kern = qmm_internal_matvec_kernel(l);           // (qmm_matvec.hip holds the instantiations)
     if (!kern) return fail(QMM_EINVAL, l.kind == MV_PER_TYPE ? "matvec: N=%d" : "kmix matvec: N=%d", l.ntok);
     if (l.lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) l.lds));
     if (c->trace) { l.text(text, sizeof(text)); QMM_TRACE(c, "%s", text); }
-    hipLaunchKernelGGL(kern, dim3(l.blocks), dim3(l.waves * WAVE), l.lds, st, g, x, ldx, l.K, l.act_arg, g.row_end[g.n - 1]);
+    hipLaunchKernelGGL(kern, dim3(l.blocks), dim3(l.waves * WAVE), l.lds, st, x, ldx, l.K, l.act_arg, g.row_end[g.n - 1], g);
     HIP_TRY(hipGetLastError());
     return QMM_OK;
 }
@@ -508,6 +492,7 @@ int qmm_set_codebook(qmm_ctx * c, int type, const uint32_t * entries, int n_entr
     HIP_TRY(hipDeviceSynchronize());                             // no launch in flight reads a table while it changes
     HIP_TRY(codebook_upload(type, entries, n_entries));
     if (const int rc = qmm_internal_ops_codebook(type, entries, n_entries)) return rc;
+    if (const int rc = qmm_internal_matvec_codebook(type, entries, n_entries)) return rc;
     c->codebook[codebook_slot(type)] = true;
     return QMM_OK;
 }

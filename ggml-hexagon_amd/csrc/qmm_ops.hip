@@ -1099,7 +1099,7 @@ int run_glue(qmm_ctx * ctx, hipStream_t st, const GluePlan & p, const GlueArgs &
 
 } // namespace
 
-// qmm_set_codebook (qmm_api.hip) writes both code objects' tables (IQ3, IQ2 and the IQ1 grid alike): this one's serves get_rows_q_kernel
+// qmm_set_codebook (qmm_api.hip) writes every code object's tables (IQ3, IQ2 and the IQ1 grid alike): this one's serves get_rows_q_kernel
 int qmm_internal_ops_codebook(int type, const uint32_t * entries, int n) {
     HIP_TRY(codebook_upload(type, entries, n));
     return QMM_OK;

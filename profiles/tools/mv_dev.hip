@@ -1,13 +1,16 @@
 // mv_dev.hip — development harness of the one-token mat-vec launch (csrc/qmm_matvec.hiph matvec_kernel<T, 1, false>): the llama3-8b
 // token-generation launches that one kernel type serves, each on rotating weight sets larger than the Infinity Cache, grid / block /
 // LDS bytes as the launch plan has them (csrc/qmm_matvec_plan.h).  Built with and without the workgroup barrier between the
-// activation loads and the weight requests (MV_ACT_FIRST, qmm_matvec.hiph), timed and stamped:
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize [-DMV_ACT_FIRST=0] -o mv_dev profiles/tools/mv_dev.hip && ./mv_dev
+// activation loads and the weight requests (MV_ACT_FIRST, qmm_matvec.hiph), with the row lookup behind the activation loads or at
+// kernel entry (MV_HEAD_FIRST), with or without kernel-argument preload, timed and stamped.  The mixed-type q/k/v launch goes through
+// matvec_kmix_kernel<1, false>.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize [-DMV_ACT_FIRST=0] [-DMV_HEAD_FIRST=0]
+//         [-mllvm -amdgpu-kernarg-preload-count=8] -o mv_dev profiles/tools/mv_dev.hip && ./mv_dev
 //       times the launches, replayed from a hipGraph: median and spread of 15 windows; prints a checksum of the outputs (the same in
 //       every build: the barrier moves no bit)
-//   hipcc ... [-DMV_ACT_FIRST=0] -DMV_STAMPS -o mv_dev_stamps profiles/tools/mv_dev.hip && ./mv_dev_stamps
+//   hipcc ... -DMV_STAMPS -o mv_dev_stamps profiles/tools/mv_dev.hip && ./mv_dev_stamps
 //       the 100 MHz phase stamps of wave 0 of every workgroup (never quote this build's times: read where the phases lie):
-//       entry | activations and first slice requested | the wave's staging done | barrier passed | first slice dotted | last store
+//       entry | first activation loads issued | activations and first slice requested | the wave's staging done | barrier passed | first slice dotted | last store
 //       "first slice dotted" directly behind "barrier passed" says the slice had landed during the staging.
 #include "../../ggml-hexagon_amd/csrc/qmm_matvec.hiph"
 
@@ -21,8 +24,8 @@
 using namespace qmm;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(2); } } while (0)
 
-using Kern = void (*)(MatvecGroup, const float *, int64_t, int, int, int);
-struct Shape { const char * name; int type, K, n, M[MV_MAX_GROUP]; };
+using Kern = void (*)(const float *, int64_t, int, int, int, MatvecGroup);
+struct Shape { const char * name; int type, K, n, M[MV_MAX_GROUP]; bool mixed; };   // mixed: the last matrix is planar Q6_K
 
 int main() {
     setvbuf(stdout, nullptr, _IONBF, 0);
@@ -35,15 +38,23 @@ int main() {
         { "q/k/v Q4_K 4096+1024+1024 x 4096",  T_Q4_K,  4096,  3, { 4096, 1024, 1024 } },
         { "wo Q4_K 4096 x 4096",               T_Q4_K,  4096,  1, { 4096 } },
         { "gate+up Q4_K 2 x 14336 x 4096",     T_Q4_K,  4096,  2, { 14336, 14336 } },
+        { "q/k/v mixed 4096+1024 Q4_K, 1024 planar Q6_K x 4096", T_Q4_K, 4096, 3, { 4096, 1024, 1024 }, true },
+        { "output planar Q6_K 128256 x 4096",  T_Q6_KP, 4096,  1, { 128256 } },
     };
     std::mt19937 rng(7);
     hipStream_t st;
     CK(hipStreamCreate(&st));
     for (const Shape & s : shapes) {
-        const int64_t rb = (int64_t) s.K / 256 * (s.type == T_Q4_K ? 144 : 210);
-        int row_end[MV_MAX_GROUP], rows = 0;
-        for (int i = 0; i < s.n; ++i) row_end[i] = rows += s.M[i];
-        const size_t bytes = (size_t) rows * rb;
+        int64_t rbs[MV_MAX_GROUP];
+        int types[MV_MAX_GROUP], row_end[MV_MAX_GROUP], rows = 0;
+        size_t offs[MV_MAX_GROUP], bytes = 0;
+        for (int i = 0; i < s.n; ++i) {
+            types[i] = s.mixed && i == s.n - 1 ? T_Q6_KP : s.type;
+            rbs[i] = (int64_t) s.K / 256 * (types[i] == T_Q4_K ? 144 : 210);
+            row_end[i] = rows += s.M[i];
+            offs[i] = bytes;
+            bytes += (size_t) s.M[i] * rbs[i];
+        }
         const int sets = (int) std::min<size_t>(48, ((size_t) 320 << 20) / bytes + 2);
         // every byte below 0x40: finite f16 scales whatever field a byte lands in (the values do not matter, their bits must agree)
         std::vector<uint8_t> hw(bytes);
@@ -55,19 +66,19 @@ int main() {
         for (int k = 0; k < sets; ++k) CK(hipMemcpy(w + bytes * k, hw.data(), bytes, hipMemcpyHostToDevice));
         CK(hipMemcpy(x, hx.data(), s.K * 4, hipMemcpyHostToDevice));
         const MatvecRules rules = { cus, 1, 2, 1, QMM_ACT_REF };
-        const MatvecLaunch plan = matvec_launch(rules, MV_PER_TYPE, s.type, nullptr, row_end, s.n, s.K, 0, 1, false, 0, nullptr);
+        const MatvecLaunch plan = matvec_launch(rules, s.mixed ? MV_MIXED : MV_PER_TYPE, s.type, nullptr, row_end, s.n, s.K, 0, 1, false, 0, nullptr);
         if (plan.error) { fprintf(stderr, "%s: refused\n", s.name); return 2; }
-        const Kern kern = s.type == T_Q4_K ? matvec_kernel<T_Q4_K, 1, false> : matvec_kernel<T_Q6_KP, 1, false>;
+        const Kern kern = s.mixed ? matvec_kmix_kernel<1, false> : s.type == T_Q4_K ? matvec_kernel<T_Q4_K, 1, false> : matvec_kernel<T_Q6_KP, 1, false>;
         auto launch = [&](int set) {
             MatvecGroup g;
             memset(&g, 0, sizeof(g));
             for (int i = 0; i < s.n; ++i) {
-                g.w[i] = w + bytes * set + (size_t) (i ? row_end[i - 1] : 0) * rb;
+                g.w[i] = w + bytes * set + offs[i];
                 g.dst[i] = dst + (i ? row_end[i - 1] : 0);
-                g.row_bytes[i] = rb;  g.ldd[i] = s.M[i];  g.row_end[i] = row_end[i];  g.type[i] = s.type;
+                g.row_bytes[i] = rbs[i];  g.ldd[i] = s.M[i];  g.row_end[i] = row_end[i];  g.type[i] = types[i];
             }
             g.n = s.n;
-            hipLaunchKernelGGL(kern, dim3(plan.blocks), dim3(plan.waves * WAVE), plan.lds, st, g, x, (int64_t) s.K, s.K, plan.act_arg, rows);
+            hipLaunchKernelGGL(kern, dim3(plan.blocks), dim3(plan.waves * WAVE), plan.lds, st, x, (int64_t) s.K, s.K, plan.act_arg, rows, g);
         };
         std::vector<float> o(rows);
         CK(hipMemsetAsync(dst, 0xff, (size_t) rows * 4, st));
@@ -76,10 +87,11 @@ int main() {
         CK(hipMemcpy(o.data(), dst, (size_t) rows * 4, hipMemcpyDeviceToHost));
         uint32_t sum = 0;
         for (float v : o) { uint32_t u; memcpy(&u, &v, 4); sum = sum * 31 + u; }
-        printf("%-36s %5.1f MB x %2d sets, grid %d x %d, barrier %s, output bits %08x\n", s.name, bytes / 1e6, sets, plan.blocks, plan.waves * WAVE, MV_ACT_FIRST ? "on" : "off", sum);
+        printf("%-36s %5.1f MB x %2d sets, grid %d x %d, barrier %s, head %s, output bits %08x\n", s.name, bytes / 1e6, sets, plan.blocks, plan.waves * WAVE, MV_ACT_FIRST ? "on" : "off", MV_HEAD_FIRST ? "new" : "old", sum);
 #ifdef MV_STAMPS
-        static const char * names[6] = { "entry", "requests out", "own staging done", "barrier passed", "first slice dotted", "last store" };
-        {
+        static const char * names[7] = { "entry", "first act load", "requests out", "own staging done", "barrier passed", "first slice dotted", "last store" };
+        static const int slot[7] = { 0, 6, 1, 2, 3, 4, 5 };
+        if (!s.mixed) {                                                        // (matvec_kmix_kernel carries no stamps)
             for (int k = 0; k < sets; ++k) launch(k);                          // the stamped launch reads a set that has left the cache
             CK(hipStreamSynchronize(st));
             static unsigned long long stamps[512][8];
@@ -88,9 +100,9 @@ int main() {
             unsigned long long t0 = ~0ull;
             for (int b = 0; b < nb; ++b) t0 = std::min(t0, stamps[b][0]);
             printf("  us from the first workgroup's entry, median / max over %d workgroups:", nb);
-            for (int k = 0; k < 6; ++k) {
+            for (int k = 0; k < 7; ++k) {
                 std::vector<double> v;
-                for (int b = 0; b < nb; ++b) v.push_back((double) (stamps[b][k] - t0) / 100.0);
+                for (int b = 0; b < nb; ++b) v.push_back((double) (stamps[b][slot[k]] - t0) / 100.0);
                 std::sort(v.begin(), v.end());
                 printf("%s %s %.2f / %.2f", k ? " |" : "", names[k], v[nb / 2], v[nb - 1]);
             }
