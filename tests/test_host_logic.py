@@ -833,6 +833,37 @@ static std::string plan_line(const std::string & spec) {
         return b;
     }
     MatvecRules r = { 256, 1, 2, 1, QMM_ACT_REF };                  // qmm_ctx's defaults
+    if (what == "sweep") {
+        // sweep types: whatever a fit estimate accepts, the launch it stands for asks for no more than MV_LDS_LAUNCH: every type, 1 .. 8
+        // tokens, K in multiples of the type's block (planar rows: of 256) up to 32768, as mv_same_bytes walks them
+        in >> ts;
+        long long checked = 0;
+        size_t worst = 0;
+        const int re[1] = { 8 };
+        auto over = [&](int kind, int type, int K, int n, bool norm, int swiglu, const char * fit) {
+            const MatvecLaunch l = matvec_launch(r, kind, type, nullptr, re, 1, K, 0, n, norm, swiglu, nullptr);
+            ++checked;
+            if (l.lds > worst) worst = l.lds;
+            if (l.lds <= MV_LDS_LAUNCH) return false;
+            snprintf(b, sizeof(b), "sweep violation: %s accepts kind %d type %d n=%d K=%d, the launch needs %zu B", fit, kind, type, n, K, l.lds);
+            return true;
+        };
+        for (int64_t type : csv(ts)) {
+            const int ty = (int) type, step = type_planar(ty) ? 256 : type_blck(ty);
+            for (int K = step; K <= 32768; K += step) for (int n = 1; n <= QMM_MATVEC_MAX_N; ++n) {
+                if (mv_fits_plain(n, K) && over(MV_PER_TYPE, ty, K, n, false, 0, "mv_fits_plain")) return b;
+                if (mv_fits_norm(n, K) && over(MV_PER_TYPE, ty, K, n, true, 0, "mv_fits_norm")) return b;
+                if (mv_fits_swiglu(n, K, false) && over(MV_PER_TYPE, ty, K, n, false, 1, "mv_fits_swiglu")) return b;
+                if (mv_fits_swiglu(n, K, true) && over(MV_PER_TYPE, ty, K, n, true, 1, "mv_fits_swiglu with the norm")) return b;
+                if (K % 256) continue;
+                if (mv_fits_mixed(n, K) && over(MV_MIXED, ty, K, n, false, 0, "mv_fits_mixed")) return b;
+                if (mv_fits_mixed(n, K) && mv_fits_norm(n, K) && over(MV_MIXED, ty, K, n, true, 0, "mv_fits_mixed with the norm")) return b;
+                if (mv_fits_mixed_q80(n, K) && n <= 4 && over(MV_MIXED_Q80, ty, K, n, false, 0, "mv_fits_mixed_q80")) return b;
+            }
+        }
+        snprintf(b, sizeof(b), "sweep ok: %lld launches, the largest %zu B", checked, worst);
+        return b;
+    }
     int64_t K, N = 1;
     in >> r.cus >> ts >> ms >> K;
     if (what == "group") in >> N;
