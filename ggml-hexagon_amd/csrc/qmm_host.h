@@ -68,6 +68,8 @@ struct qmm_ctx {
     // The attention labels are the plan's (qmm_attn_plan.h), spelled as rocprofv3 prints the kernels:
     //   attn_decode_short_kernel<D,fresh,width>   attn_decode_kernel<D,fresh>   attn_decode_split_kernel<D> then attn_combine_kernel   attn_prefill_kernel<D>
     //   attn_rows_decode_kernel<D> (a cut cache: then attn_combine_kernel)   attn_rows_prefill_kernel<D>      (QMM_TENSOR_KV_ROWS: FLASH_ATTN_EXT's operands)
+    // A Q8_0 K cache (qmm_kcache.hiph; labels of qmm_kcache_plan.h): cpy_q8_0_quantize_kernel, cpy_q8_0_unpack_kernel<f32|f16>,
+    //   attn_kq8_decode_kernel<D> (a cut cache: then attn_combine_kernel); the prompt form: cpy_q8_0_unpack_kernel<f16> then attn_prefill_kernel<D>
     // Untraced, a launch pays one pointer test.
     std::string * trace = nullptr;
 

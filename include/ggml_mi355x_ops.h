@@ -43,7 +43,10 @@ enum qmm_op {
     QMM_OP_RMS_NORM,          /* op_params[0] = eps (f32) */
     QMM_OP_ROPE,              /* src1 = positions (i32), src2 = frequency factors (f32) or NULL; op_params as ggml_rope_ext */
     QMM_OP_SOFT_MAX,          /* src1 = mask (f32 / f16) or NULL; op_params = {scale, max_bias} */
-    QMM_OP_CPY,               /* also CONT and DUP: src0 -> dst, any strides, F32 / F16 either side */
+    QMM_OP_CPY,               /* also CONT and DUP: src0 -> dst, any strides, F32 / F16 either side; and for a Q8_0 K cache (type 8, blocks of
+                                 one f16 d and 32 int8): F32 (ne0 % 32 == 0, rows dense, any 4-byte strides) -> contiguous Q8_0, the bytes of the
+                                 CPU backend's quantize_row_q8_0 in the context's act mode, and Q8_0 (blocks dense in a row, 2-byte strides) ->
+                                 contiguous F32 / F16, f32(d) * q; element i of src in src's index order is element i of dst */
     QMM_OP_GET_ROWS,          /* src0 rows (F32 / F16 / every quantized weight type of ggml_mi355x_qmm.h) picked by src1 (i32) -> f32 */
     QMM_OP_MUL_MAT_F,         /* src0 F16 or F32 (any row strides, broadcast over dims 2/3), src1 F32 -> f32 */
     /* fused pairs the plugin forms from consecutive nodes */
@@ -86,7 +89,12 @@ QMM_API int qmm_op_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * a, const qmm_t
  *   q    f32 [D, N, H]       (any row / head strides)        k  f16 [D, n_kv, H_kv]   rows dense, 16-byte aligned
  *   v    f16 [Dv, n_kv, H_kv] rows dense, row and head strides 16-byte aligned, as k
  *   mask f32 or f16 [n_kv, >= N]                             dst f32 [Dv * H, N]       (the op's [Dv, H, N])
- * D = Dv in {64, 128}, n_kv a multiple of 64 up to 16384 (llama.cpp pads it to 256 with flash attention), H a multiple of H_kv. */
+ * D = Dv in {64, 128}, n_kv a multiple of 64 up to 16384 (llama.cpp pads it to 256 with flash attention), H a multiple of H_kv.
+ *
+ * With k->type == 8 (a Q8_0 K cache, llama.cpp's -ctk q8_0 without flash attention; v->flags == 0): the first chain with
+ *   k    Q8_0 [D, n_kv, H_kv]  blocks dense in a row (nb[0] == 34), nb[1] and nb[2] multiples of 2 (llama.cpp: nb[2] = 34 D / 32, nb[1] = H_kv nb[2])
+ * and every other operand as there.  D in {64, 128}, Dv <= 128, N <= 8, n_kv a multiple of 32 up to 16384.  Scores in the CPU path's arithmetic
+ * for a Q8_0 src0: q quantized to Q8_0 per 32 values in the context's act mode, integer dots times d_k * d_q, f32 sums in block order. */
 QMM_API int qmm_attn_decode_supported(const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
                                       const qmm_tensor * dst);
 QMM_API int qmm_attn_decode(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
@@ -98,7 +106,11 @@ QMM_API int qmm_attn_decode(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tenso
  * Longer caches are walked 512 columns at a time with a running maximum and sum per token row.
  *
  * With v->flags == QMM_TENSOR_KV_ROWS: the flash-attention operands described at qmm_attn_decode, for any N >= 1; D = Dv in
- * {64, 128}, n_kv a multiple of 64, q rows and heads 16-byte aligned. */
+ * {64, 128}, n_kv a multiple of 64, q rows and heads 16-byte aligned.
+ *
+ * With k->type == 8 (k as described at qmm_attn_decode, v->flags == 0): D = Dv in {64, 128}, n_kv a multiple of 32.  One launch unpacks the
+ * n_kv x H_kv K rows to f16 (k = f16(f32(d) * q)) into the context's workspace, at most 64 MiB of it (2 D n_kv H_kv bytes; beyond: not
+ * supported), then the launch above runs on that image: its arithmetic, bit for bit. */
 QMM_API int qmm_attn_prefill_supported(const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
                                        const qmm_tensor * dst);
 QMM_API int qmm_attn_prefill(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
@@ -107,7 +119,7 @@ QMM_API int qmm_attn_prefill(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tens
 /* What follows the q / k / v projections of a few-token batch in build_attn (src/llama-graph.cpp:1306-1365), in one launch:
  *   q_dst = rope(q) (f32; q_dst carries the ROPE node's op_params), k_dst = (f16) rope(k) straight into the K cache view,
  *   v_dst = (f16) v into the (transposed) V cache view, element i of v (in v's index order) to element i of v_dst, as CPY does.
- * k / k_dst and v / v_dst are optional pairs (NULL). */
+ * k / k_dst and v / v_dst are optional pairs (NULL).  A Q8_0 k_dst is refused: a Q8_0 K cache is stored by ROPE and QMM_OP_CPY. */
 QMM_API int qmm_rope_kv_store_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
                                         const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst);
 QMM_API int qmm_rope_kv_store(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
@@ -153,7 +165,8 @@ QMM_API int qmm_moe_combine_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * x, co
  * D <= 128): q [D, H, N] arrives un-roped (q_rope: the ROPE node's descriptor, for its op_params), k_new [D, H_kv, N] and
  * v_new (v_cur^T, [N, Dv * H_kv]) are the batch's projections, k_store / v_store where qmm_rope_kv_store would put them, k / v the
  * cache views the attention reads, j0 the cache row of the batch's first token.  Every workgroup forms the new rows it needs
- * itself and takes them from LDS, so nothing reads rows j0 .. j0 + N of the cache while one workgroup per kv head stores them. */
+ * itself and takes them from LDS, so nothing reads rows j0 .. j0 + N of the cache while one workgroup per kv head stores them.
+ * F16 caches only: a Q8_0 k_store or k is refused. */
 QMM_API int qmm_attn_decode_rope_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_rope,
                                            const qmm_tensor * k_new, const qmm_tensor * k_store, const qmm_tensor * v_new,
                                            const qmm_tensor * v_store, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
