@@ -57,9 +57,10 @@ bool supports_mul_mat(const struct ggml_tensor * op) {
     if (is_split(a) && (a->ne[2] != 1 || a->ne[3] != 1 || b->ne[2] != 1 || b->ne[3] != 1)) return false;
     if (b->nb[1] < b->ne[0] * sizeof(float)) return false;                          // transposed / permuted src1
     if (b->ne[2] % a->ne[2] || b->ne[3] % a->ne[3]) return false;
-    // a Q8_0 src0 may be permuted / strided in dims 1-3 (the view of a Q8_0 K cache that kq reads; mul_mat_shape_ok has asked for dense
-    // blocks and even strides): issue_mul_mat_broadcast takes one row stride per (i12, i13), and weight_type never re-lays such a tensor
-    if (a->type == GGML_TYPE_Q8_0 && !is_split(a)) return true;
+    // a Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 src0 may be permuted / strided in dims 1-3 (the view of a K cache of that type that kq reads;
+    // mul_mat_shape_ok has asked for dense blocks and even strides): issue_mul_mat_broadcast takes one row stride per (i12, i13) and runs
+    // the ggml-layout units, since weight_type never re-lays a tensor outside a weights buffer (nor a view that cuts a weight's rows)
+    if (kcache_block_type(a->type) && !is_split(a)) return true;
     if (a->nb[2] < a->nb[1] * (size_t) a->ne[1] || (a->ne[3] > 1 && a->nb[3] < a->nb[2] * (size_t) a->ne[2])) return false;   // permuted src0
     return true;
 }
@@ -337,7 +338,7 @@ enum ggml_status graph_compute_once(ggml_backend_t backend, struct ggml_cgraph *
                 st = compute_glue(ctx, node, gop, node->src[0], node->src[1], node->src[2]);
             }
         } else if (node->op == GGML_OP_MUL_MAT) {
-            if (node->src[0]->type == GGML_TYPE_Q8_0 && node->src[0]->view_src) {     // kq on a Q8_0 K cache is no glue op: the attention site sees it first
+            if (kcache_block_type(node->src[0]->type) && node->src[0]->view_src) {    // kq on a quantized K cache is no glue op: the attention site sees it first
                 const int r = P.offer_to_sites(i, 0);
                 if (r < 0) return GGML_STATUS_FAILED;
                 if (r > 0) continue;

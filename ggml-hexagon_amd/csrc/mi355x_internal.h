@@ -198,6 +198,11 @@ void planar_release(mi355x_buffer_ctx * bc, const char * p, size_t size, bool ov
 mi355x_buffer_ctx * our_buffer_ctx(const ggml_tensor * t);
 int dev_type(const ggml_tensor * t);
 int weight_type(mi355x_backend_ctx * ctx, const ggml_tensor * t);
+// the block types a quantized K cache comes in without flash attention (-ctk q8_0 / q4_0 / q4_1 / q5_0 / q5_1; IQ4_NL has no store on the
+// device): kq reads a permuted view of such a cache as its src0
+inline bool kcache_block_type(enum ggml_type t) {
+    return t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0 || t == GGML_TYPE_Q4_1 || t == GGML_TYPE_Q5_0 || t == GGML_TYPE_Q5_1;
+}
 
 // ----------------------------------------------------------------------------------------------- mi355x_split.cpp
 bool buft_is_split(ggml_backend_buffer_type_t buft);

@@ -55,7 +55,7 @@ graph_pass::attn_chain graph_pass::match_attention(int kq, int from, int last) c
     const ggml_tensor * kqn = cgraph->nodes[idx[0]], * sm = cgraph->nodes[idx[1]], * kqv = cgraph->nodes[idx[2]], * pm = cgraph->nodes[idx[3]],
                       * ct = cgraph->nodes[idx[4]];
     const sm_params p = soft_max_params(sm);
-    if (!(kqn->op == GGML_OP_MUL_MAT && (kqn->src[0]->type == GGML_TYPE_F16 || kqn->src[0]->type == GGML_TYPE_Q8_0) && single_use(kqn) &&
+    if (!(kqn->op == GGML_OP_MUL_MAT && (kqn->src[0]->type == GGML_TYPE_F16 || kcache_block_type(kqn->src[0]->type)) && single_use(kqn) &&
           sm->op == GGML_OP_SOFT_MAX && sm->src[0] == kqn && sm->src[1] && p.max_bias == 0.0f && single_use(sm) &&
           kqv->op == GGML_OP_MUL_MAT && kqv->src[1] == sm && kqv->src[0]->type == GGML_TYPE_F16 && single_use(kqv) &&
           pm->op == GGML_OP_PERMUTE && pm->src[0] == kqv && pm->ne[0] == kqv->ne[0] && pm->ne[1] == kqv->ne[2] && pm->ne[2] == kqv->ne[1] &&
@@ -162,8 +162,8 @@ graph_pass::combine_match graph_pass::match_moe_combine(int i) const {
 
 // Behind ROPE node i (rope(q)), among the live nodes in front of the attention: rope(k) with the same positions and parameters and its
 // store into the K cache, and v's store into the V cache (build_attn's two ggml_cpy).  Their inputs must exist already (k and v were
-// hoisted into the q/k/v group); rope(k) without its store stays where it is.  Only an F16 K store pairs with rope(k): on a Q8_0 K cache
-// (-ctk q8_0) the launch is rope(q) + the V store, rope(k) and its CPY f32 -> Q8_0 run as their own nodes, and the one-launch rope +
+// hoisted into the q/k/v group); rope(k) without its store stays where it is.  Only an F16 K store pairs with rope(k): on a quantized K cache
+// (-ctk q8_0 / q4_0 / q4_1 / q5_0 / q5_1) the launch is rope(q) + the V store, rope(k) and its CPY f32 -> block type run as their own nodes, and the one-launch rope +
 // store + attention (which needs the pair) is never tried; the attention chain is taken at its kq (site_attention).
 graph_pass::rope_kv_match graph_pass::match_rope_kv(int i) const {
     const ggml_tensor * node = cgraph->nodes[i];
@@ -531,7 +531,7 @@ int graph_pass::site_rope_kv_attention(int i) {
 // launch failed.  Where two sites start at the same kind of node their order matters:
 //   MUL       a MUL that site_hold_silu claimed carries the SILU nobody has run: it is always finished as silu * up, never
 //             looked at as the head of a MoE combine.
-//   MUL_MAT   (F16 src0, or a view of a Q8_0 K cache, which graph_compute offers although it is no glue op and which can only be a kq)
+//   MUL_MAT   (F16 src0, or a view of a K cache in a block type (kcache_block_type), which graph_compute offers although it is no glue op and which can only be a kq)
 //             the attention takes the whole chain from kq; only a kqv that no attention launch took (the chain was declined
 //             when its kq came by) is left for the merged-heads write.  The attention site may have sent ct to the scratch by then,
 //             and the merged-heads write follows it there.
@@ -548,8 +548,8 @@ int graph_pass::offer_to_sites(int i, int gop) {
             return site_moe_combine(i);
         case GGML_OP_UNARY:    return gop == QMM_OP_SILU ? site_hold_silu(i) : 0;
         case GGML_OP_ADD:      return site_add_rms_norm(i);
-        case GGML_OP_MUL_MAT:                                                   // (QMM_OP_MUL_MAT_F: src0 is F16 or F32; gop 0: a view of a Q8_0 K cache)
-            if (node->src[0]->type == GGML_TYPE_Q8_0) return site_attention(i);
+        case GGML_OP_MUL_MAT:                                                   // (QMM_OP_MUL_MAT_F: src0 is F16 or F32; gop 0: a view of a quantized K cache)
+            if (kcache_block_type(node->src[0]->type)) return site_attention(i);
             if (node->src[0]->type != GGML_TYPE_F16) return site_moe_router(i);
             r = site_attention(i);
             return r ? r : site_kqv_into_merged_heads(i);

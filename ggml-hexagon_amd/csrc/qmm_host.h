@@ -70,6 +70,8 @@ struct qmm_ctx {
     //   attn_rows_decode_kernel<D> (a cut cache: then attn_combine_kernel)   attn_rows_prefill_kernel<D>      (QMM_TENSOR_KV_ROWS: FLASH_ATTN_EXT's operands)
     // A Q8_0 K cache (qmm_kcache.hiph; labels of qmm_kcache_plan.h): cpy_q8_0_quantize_kernel, cpy_q8_0_unpack_kernel<f32|f16>,
     //   attn_kq8_decode_kernel<D> (a cut cache: then attn_combine_kernel); the prompt form: cpy_q8_0_unpack_kernel<f16> then attn_prefill_kernel<D>
+    // A K cache in T = q4_0 | q4_1 | q5_0 | q5_1 (qmm_kblk.hiph; labels of qmm_kblk_plan.h): cpy_T_quantize_kernel, cpy_T_unpack_kernel<f32|f16>,
+    //   attn_kblk_decode_kernel<T,D> (a cut cache: then attn_combine_kernel); the prompt form: cpy_T_unpack_kernel<f16> then attn_prefill_kernel<D>
     // Untraced, a launch pays one pointer test.
     std::string * trace = nullptr;
 

@@ -8,7 +8,8 @@
 // The attention launches (AttnArgs, AttnFresh, the five attn_* kernels, qmm_attn_decode / _decode_rope / _prefill and their
 // _supported predicates) are a section of their own, qmm_attn.hiph, included below in front of the entry points; what they launch
 // for a shape is decided by qmm_attn_plan.h.  What a Q8_0 K cache adds (CPY into and out of block_q8_0 rows, attention on them) is the
-// section behind it, qmm_kcache.hiph, decided by qmm_kcache_plan.h: QMM_OP_CPY and the attention entry points branch there first.
+// section behind it, qmm_kcache.hiph, decided by qmm_kcache_plan.h: QMM_OP_CPY and the attention entry points branch there first; a K cache
+// in Q4_0 / Q4_1 / Q5_0 / Q5_1 is the section behind that one, qmm_kblk.hiph (qmm_kblk_plan.h), reached the same way.
 
 #include "qmm_host.h"
 #include "qmm_glue_plan.h"
@@ -1108,17 +1109,20 @@ int qmm_internal_ops_codebook(int type, const uint32_t * entries, int n) {
 
 #include "qmm_attn.hiph"         // the attention kernels, their launch executor and entry points
 #include "qmm_kcache.hiph"       // a Q8_0 K cache: CPY into and out of block_q8_0 rows, attention on them (what runs: qmm_kcache_plan.h)
+#include "qmm_kblk.hiph"         // a K cache in Q4_0 / Q4_1 / Q5_0 / Q5_1: the same surface on those blocks (what runs: qmm_kblk_plan.h)
 
 extern "C" {
 
 int qmm_op_supported(int op, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * c, const qmm_tensor * d) {
     if (op == QMM_OP_CPY && kq8_cpy_case(a, d)) return kq8_takes_cpy(a, d);
+    if (op == QMM_OP_CPY && kblk_cpy_case(a, d)) return kblk_takes_cpy(a, d);
     return sup_op(op, a, b, c, d);
 }
 
 int qmm_op_compute(qmm_ctx * ctx, int op, const qmm_tensor * a, const qmm_tensor * b, const qmm_tensor * c, const qmm_tensor * d, void * stream) {
     if (!ctx || !d) return fail(QMM_EINVAL, "qmm_op_compute: NULL context or dst");
     if (op == QMM_OP_CPY && kq8_cpy_case(a, d)) return kq8_cpy(ctx, a, d, stream);
+    if (op == QMM_OP_CPY && kblk_cpy_case(a, d)) return kblk_cpy(ctx, a, d, stream);
     if (!sup_op(op, a, b, c, d)) return fail(QMM_EUNSUPPORTED, "qmm_op_compute: op %d with these types / shapes / strides is not implemented", op);
     if (op == QMM_OP_GET_ROWS) { const int rc = need_codebook(ctx, a->type, "qmm_op_compute(GET_ROWS)"); if (rc) return rc; }
     HIP_TRY(hipSetDevice(ctx->device));

@@ -46,7 +46,11 @@ enum qmm_op {
     QMM_OP_CPY,               /* also CONT and DUP: src0 -> dst, any strides, F32 / F16 either side; and for a Q8_0 K cache (type 8, blocks of
                                  one f16 d and 32 int8): F32 (ne0 % 32 == 0, rows dense, any 4-byte strides) -> contiguous Q8_0, the bytes of the
                                  CPU backend's quantize_row_q8_0 in the context's act mode, and Q8_0 (blocks dense in a row, 2-byte strides) ->
-                                 contiguous F32 / F16, f32(d) * q; element i of src in src's index order is element i of dst */
+                                 contiguous F32 / F16, f32(d) * q; element i of src in src's index order is element i of dst.  The same two
+                                 forms for a K cache in Q4_0 / Q4_1 / Q5_0 / Q5_1 (types 2, 3, 6, 7: blocks of 18 / 20 / 22 / 24 bytes, f16 d,
+                                 [f16 m], [4 bytes qh], 16 bytes of nibbles): F32 -> type gives the bytes of quantize_row_q4_0_ref / q4_1_ref /
+                                 q5_0_ref / q5_1_ref (the CPU backend's from_float for them; no act mode), type -> F32 / F16 the values of
+                                 dequantize_row_q4_0 / q4_1 / q5_0 / q5_1 (the f16 form rounded once more) */
     QMM_OP_GET_ROWS,          /* src0 rows (F32 / F16 / every quantized weight type of ggml_mi355x_qmm.h) picked by src1 (i32) -> f32 */
     QMM_OP_MUL_MAT_F,         /* src0 F16 or F32 (any row strides, broadcast over dims 2/3), src1 F32 -> f32 */
     /* fused pairs the plugin forms from consecutive nodes */
@@ -94,7 +98,12 @@ QMM_API int qmm_op_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * a, const qmm_t
  * With k->type == 8 (a Q8_0 K cache, llama.cpp's -ctk q8_0 without flash attention; v->flags == 0): the first chain with
  *   k    Q8_0 [D, n_kv, H_kv]  blocks dense in a row (nb[0] == 34), nb[1] and nb[2] multiples of 2 (llama.cpp: nb[2] = 34 D / 32, nb[1] = H_kv nb[2])
  * and every other operand as there.  D in {64, 128}, Dv <= 128, N <= 8, n_kv a multiple of 32 up to 16384.  Scores in the CPU path's arithmetic
- * for a Q8_0 src0: q quantized to Q8_0 per 32 values in the context's act mode, integer dots times d_k * d_q, f32 sums in block order. */
+ * for a Q8_0 src0: q quantized to Q8_0 per 32 values in the context's act mode, integer dots times d_k * d_q, f32 sums in block order.
+ *
+ * With k->type in {2, 3, 6, 7} (a K cache in Q4_0 / Q4_1 / Q5_0 / Q5_1; v->flags == 0): the same operands and limits with this type's block
+ * size in k->nb[0] (18 / 20 / 22 / 24).  Scores in the CPU path's arithmetic for such a src0: q quantized in the context's act mode to Q8_0
+ * (Q4_0 / Q5_0) or Q8_1 (Q4_1 / Q5_1: d and s = d * sum), integer dots, then sumi * d_k * d_q (Q4_0), (d_k * d_q) * sumi (Q5_0),
+ * (d_k * d_q) * sumi + m_k * s_q (Q4_1 / Q5_1), every operation rounded on its own, f32 sums in block order. */
 QMM_API int qmm_attn_decode_supported(const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
                                       const qmm_tensor * dst);
 QMM_API int qmm_attn_decode(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
@@ -110,7 +119,9 @@ QMM_API int qmm_attn_decode(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tenso
  *
  * With k->type == 8 (k as described at qmm_attn_decode, v->flags == 0): D = Dv in {64, 128}, n_kv a multiple of 32.  One launch unpacks the
  * n_kv x H_kv K rows to f16 (k = f16(f32(d) * q)) into the context's workspace, at most 64 MiB of it (2 D n_kv H_kv bytes; beyond: not
- * supported), then the launch above runs on that image: its arithmetic, bit for bit. */
+ * supported), then the launch above runs on that image: its arithmetic, bit for bit.
+ *
+ * With k->type in {2, 3, 6, 7} (k as described at qmm_attn_decode, v->flags == 0): the same, the image holding k = f16(dequantize_row_*). */
 QMM_API int qmm_attn_prefill_supported(const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
                                        const qmm_tensor * dst);
 QMM_API int qmm_attn_prefill(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
@@ -119,7 +130,8 @@ QMM_API int qmm_attn_prefill(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tens
 /* What follows the q / k / v projections of a few-token batch in build_attn (src/llama-graph.cpp:1306-1365), in one launch:
  *   q_dst = rope(q) (f32; q_dst carries the ROPE node's op_params), k_dst = (f16) rope(k) straight into the K cache view,
  *   v_dst = (f16) v into the (transposed) V cache view, element i of v (in v's index order) to element i of v_dst, as CPY does.
- * k / k_dst and v / v_dst are optional pairs (NULL).  A Q8_0 k_dst is refused: a Q8_0 K cache is stored by ROPE and QMM_OP_CPY. */
+ * k / k_dst and v / v_dst are optional pairs (NULL).  A Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 k_dst is refused: a quantized
+ * K cache is stored by ROPE and QMM_OP_CPY. */
 QMM_API int qmm_rope_kv_store_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
                                         const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst);
 QMM_API int qmm_rope_kv_store(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
@@ -166,7 +178,7 @@ QMM_API int qmm_moe_combine_add_rms_norm(qmm_ctx * ctx, const qmm_tensor * x, co
  * v_new (v_cur^T, [N, Dv * H_kv]) are the batch's projections, k_store / v_store where qmm_rope_kv_store would put them, k / v the
  * cache views the attention reads, j0 the cache row of the batch's first token.  Every workgroup forms the new rows it needs
  * itself and takes them from LDS, so nothing reads rows j0 .. j0 + N of the cache while one workgroup per kv head stores them.
- * F16 caches only: a Q8_0 k_store or k is refused. */
+ * F16 caches only: a Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 k_store or k is refused. */
 QMM_API int qmm_attn_decode_rope_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_rope,
                                            const qmm_tensor * k_new, const qmm_tensor * k_store, const qmm_tensor * v_new,
                                            const qmm_tensor * v_store, const qmm_tensor * k, const qmm_tensor * v, const qmm_tensor * mask,
