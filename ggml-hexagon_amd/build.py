@@ -30,7 +30,7 @@ def _newer(target: Path, sources) -> bool:
 
 def build_qmm(force: bool = False) -> Path:
     """the kernel library behind include/ggml_mi355x_qmm.h and include/ggml_mi355x_ops.h: one object per translation unit
-    (qmm_api.hip = the quantized MUL_MAT path with, as its section qmm_prefill.hiph, the prompt-batch launches, qmm_matvec.hip = the few-token mat-vec kernels, the one unit compiled with kernel-argument preload, qmm_ops.hip = the glue ops (what they launch: qmm_glue_plan.h) and, as its sections qmm_attn.hiph (with qmm_attn_rows.hiph), the attention launches, qmm_kcache.hiph, the Q8_0 K cache, and qmm_kblk.hiph, a K cache in Q4_0 / Q4_1 / Q5_0 / Q5_1 (planned by qmm_kcache_plan.h and qmm_kblk_plan.h), qmm_comm.hip = the RCCL exchange of a one-process row split), rebuilt only when its sources changed"""
+    (qmm_api.hip = the quantized MUL_MAT path with, as its section qmm_prefill.hiph, the prompt-batch launches, qmm_matvec.hip = the few-token mat-vec kernels, the one unit compiled with kernel-argument preload, qmm_ops.hip = the glue ops (what they launch: qmm_glue_plan.h) and, as its sections qmm_attn.hiph (with qmm_attn_rows.hiph), the attention launches, qmm_kcache.hiph, the Q8_0 K cache, qmm_kblk.hiph, a K cache in Q4_0 / Q4_1 / Q5_0 / Q5_1, and qmm_ropekq.hiph, the one-launch rope and store into such caches (planned by qmm_kcache_plan.h, qmm_kblk_plan.h and qmm_ropekq_plan.h), qmm_comm.hip = the RCCL exchange of a one-process row split), rebuilt only when its sources changed"""
     headers = sorted(CSRC.glob("qmm_*.hiph")) + sorted(CSRC.glob("qmm_*.h")) + sorted((ROOT / "include").glob("ggml_mi355x_*.h"))
     units = [CSRC / "qmm_api.hip", CSRC / "qmm_matvec.hip", CSRC / "qmm_ops.hip", CSRC / "qmm_comm.hip"]
     if not force and _newer(QMM_SO, units + headers):

@@ -17,6 +17,9 @@
 #include "ggml_mi355x_ops.h"
 // the module must load against a kernel library that has no qmm_set_codebook (ggml opens backends with RTLD_NOW): a weak reference, null then
 #pragma weak qmm_set_codebook
+// ... or no qmm_rope_kq_store (the one-launch rope + store on a quantized K cache): null then, and rope(k) and its CPY run as their own nodes
+#pragma weak qmm_rope_kq_store_supported
+#pragma weak qmm_rope_kq_store
 #include "qmm_switches.h"
 #include "qmm_matvec_plan.h"
 

@@ -162,9 +162,10 @@ graph_pass::combine_match graph_pass::match_moe_combine(int i) const {
 
 // Behind ROPE node i (rope(q)), among the live nodes in front of the attention: rope(k) with the same positions and parameters and its
 // store into the K cache, and v's store into the V cache (build_attn's two ggml_cpy).  Their inputs must exist already (k and v were
-// hoisted into the q/k/v group); rope(k) without its store stays where it is.  Only an F16 K store pairs with rope(k): on a quantized K cache
-// (-ctk q8_0 / q4_0 / q4_1 / q5_0 / q5_1) the launch is rope(q) + the V store, rope(k) and its CPY f32 -> block type run as their own nodes, and the one-launch rope +
-// store + attention (which needs the pair) is never tried; the attention chain is taken at its kq (site_attention).
+// hoisted into the q/k/v group); rope(k) without its store stays where it is.  A contiguous K store pairs with rope(k) when it is F16, or in a
+// block type of a quantized K cache (-ctk q8_0 / q4_0 / q4_1 / q5_0 / q5_1: kcache_block_type) and the kernel library has qmm_rope_kq_store
+// (an older library, or the stub, has not: rope(k) and its CPY f32 -> block type then run as their own nodes).  The one-launch rope + store
+// + attention stays F16 only: on a quantized cache the site never tries it, and the attention chain is taken at its kq (site_attention).
 graph_pass::rope_kv_match graph_pass::match_rope_kv(int i) const {
     const ggml_tensor * node = cgraph->nodes[i];
     auto ready = [&](const ggml_tensor * t) {                                // was t's root produced before this point?
@@ -180,7 +181,8 @@ graph_pass::rope_kv_match graph_pass::match_rope_kv(int i) const {
             !memcmp(t->op_params, node->op_params, sizeof(t->op_params)) && t->type == GGML_TYPE_F32 && ggml_is_contiguous(t) &&
             single_use(t) && ready(t->src[0])) {
             jk = j;
-        } else if (jk >= 0 && jck < 0 && t->op == GGML_OP_CPY && t->src[0] == cgraph->nodes[jk] && t->type == GGML_TYPE_F16 && ggml_is_contiguous(t)) {
+        } else if (jk >= 0 && jck < 0 && t->op == GGML_OP_CPY && t->src[0] == cgraph->nodes[jk] && ggml_is_contiguous(t) &&
+                   (t->type == GGML_TYPE_F16 || (kcache_block_type(t->type) && qmm_rope_kq_store_supported && qmm_rope_kq_store))) {
             jck = j;
         } else if (jcv < 0 && t->op == GGML_OP_CPY && t->type == GGML_TYPE_F16 && t->src[0]->type == GGML_TYPE_F32 &&
                    root_of(t->src[0])->op == GGML_OP_MUL_MAT && ready(t->src[0]) && (jk < 0 || t->src[0] != cgraph->nodes[jk])) {
@@ -478,14 +480,22 @@ int graph_pass::site_rope_kv_attention(int i) {
     const qmm_tensor q = to_qt(node->src[0], ctx), pos = to_qt(node->src[1], ctx), qd = to_qt(node, ctx);
     qmm_tensor ff{}, k{}, kd{}, v{}, vd{};
     if (node->src[2]) ff = to_qt(node->src[2], ctx);
+    bool kq = false;                                                   // the K store goes into blocks of a quantized cache
     if (s.rk >= 0) {
-        const ggml_tensor * rk = cgraph->nodes[s.rk];
+        const ggml_tensor * rk = cgraph->nodes[s.rk], * ck = cgraph->nodes[s.ck];
+        kq = kcache_block_type(ck->type);
         k = to_qt(rk->src[0], ctx);
         kd = to_qt(rk, ctx);                                           // shape of rope(k), bytes of the cache view
-        kd.data = cgraph->nodes[s.ck]->data;
-        kd.type = GGML_TYPE_F16;
-        kd.nb[0] = 2;
-        for (int a = 1; a < 4; ++a) kd.nb[a] = kd.nb[a - 1] * kd.ne[a - 1];
+        kd.data = ck->data;
+        kd.type = ck->type;
+        if (kq) {                                                      // rows of whole blocks in the type's strides (rope(k)->ne[0] is a multiple of the block, or the library declines)
+            kd.nb[0] = (int64_t) ggml_type_size(ck->type);
+            kd.nb[1] = (int64_t) ggml_row_size(ck->type, kd.ne[0]);
+            for (int a = 2; a < 4; ++a) kd.nb[a] = kd.nb[a - 1] * kd.ne[a - 1];
+        } else {
+            kd.nb[0] = 2;
+            for (int a = 1; a < 4; ++a) kd.nb[a] = kd.nb[a - 1] * kd.ne[a - 1];
+        }
     }
     if (s.cv >= 0) {
         v = to_qt(cgraph->nodes[s.cv]->src[0], ctx);
@@ -493,10 +503,24 @@ int graph_pass::site_rope_kv_attention(int i) {
     }
     const qmm_tensor * pff = node->src[2] ? &ff : nullptr, * pk = s.rk >= 0 ? &k : nullptr, * pkd = s.rk >= 0 ? &kd : nullptr,
                      * pv = s.cv >= 0 ? &v : nullptr, * pvd = s.cv >= 0 ? &vd : nullptr;
+    if (kq) {
+        // one launch for rope(q), rope(k) into the cache's blocks and the V store; the cache is stored early as on F16.  Declined: the K
+        // pair is dropped, rope(k) and its CPY stay their own nodes, and the launch below is rope(q) + the V store as before
+        if (kd.ne[0] % ggml_blck_size((enum ggml_type) kd.type) == 0 && qmm_rope_kq_store_supported(&q, &pos, pff, &qd, pk, pkd, pv, pvd)) {
+            const int rc = qmm_rope_kq_store(qc, &q, &pos, pff, &qd, pk, pkd, pv, pvd, qmm_stream(qc));
+            if (launched(rc, "MI355X rope + quantized K store(%s): %s\n", node->name) != GGML_STATUS_SUCCESS) return -1;
+            if (dbg()) fprintf(stderr, "fused: rope + quantized k store (%s, %s)\n", cgraph->nodes[s.rk]->name, ggml_type_name(cgraph->nodes[s.ck]->type));
+            for (int j : { s.rk, s.ck, s.cv }) if (j >= 0) done[j] = 1;
+            return 1;
+        }
+        if (s.cv < 0) return 0;
+        pk = pkd = nullptr;
+    }
+    const bool k_pair = pk != nullptr;
     attn_chain c;                                                          // stays empty unless the attention goes into the launch
     qmm_tensor kc{}, vc{}, m{}, d{};
     int64_t j0 = -1;
-    if (s.rk >= 0 && s.cv >= 0 && node->ne[2] <= 8 && single_use(node) && sw().attn_rope) {
+    if (k_pair && s.cv >= 0 && node->ne[2] <= 8 && single_use(node) && sw().attn_rope) {
         c = match_attention(-1, std::max(s.ck, s.cv) + 1, i + 4 * LOOKAHEAD);
         bool ok = false;
         if (c.kq >= 0) {
@@ -520,7 +544,7 @@ int graph_pass::site_rope_kv_attention(int i) {
                              : qmm_rope_kv_store(qc, &q, &pos, pff, &qd, pk, pkd, pv, pvd, qmm_stream(qc));
     if (launched(rc, "MI355X %s(%s): %s\n", c.kq >= 0 ? "rope + KV store + attention" : "rope + KV store", node->name) != GGML_STATUS_SUCCESS) return -1;
     if (c.kq >= 0 && dbg()) fprintf(stderr, "fused: rope + kv store + attention (%s)\n", node->name);
-    for (int j : { s.rk, s.ck, s.cv, c.kq, c.sm, c.kqv, c.pm, c.ct }) if (j >= 0) done[j] = 1;
+    for (int j : { k_pair ? s.rk : -1, k_pair ? s.ck : -1, s.cv, c.kq, c.sm, c.kqv, c.pm, c.ct }) if (j >= 0) done[j] = 1;
     return 1;
 }
 

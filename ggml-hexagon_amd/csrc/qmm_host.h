@@ -72,6 +72,7 @@ struct qmm_ctx {
     //   attn_kq8_decode_kernel<D> (a cut cache: then attn_combine_kernel); the prompt form: cpy_q8_0_unpack_kernel<f16> then attn_prefill_kernel<D>
     // A K cache in T = q4_0 | q4_1 | q5_0 | q5_1 (qmm_kblk.hiph; labels of qmm_kblk_plan.h): cpy_T_quantize_kernel, cpy_T_unpack_kernel<f32|f16>,
     //   attn_kblk_decode_kernel<T,D> (a cut cache: then attn_combine_kernel); the prompt form: cpy_T_unpack_kernel<f16> then attn_prefill_kernel<D>
+    // qmm_rope_kq_store (qmm_ropekq.hiph; label of qmm_ropekq_plan.h), T = q8_0 | q4_0 | q4_1 | q5_0 | q5_1: rope_kq_store_kernel<T,true|false> (true: the v part goes through tiles)
     // Untraced, a launch pays one pointer test.
     std::string * trace = nullptr;
 

@@ -1110,6 +1110,7 @@ int qmm_internal_ops_codebook(int type, const uint32_t * entries, int n) {
 #include "qmm_attn.hiph"         // the attention kernels, their launch executor and entry points
 #include "qmm_kcache.hiph"       // a Q8_0 K cache: CPY into and out of block_q8_0 rows, attention on them (what runs: qmm_kcache_plan.h)
 #include "qmm_kblk.hiph"         // a K cache in Q4_0 / Q4_1 / Q5_0 / Q5_1: the same surface on those blocks (what runs: qmm_kblk_plan.h)
+#include "qmm_ropekq.hiph"       // rope(q), rope(k) into a K cache of any of those five block types and the V store as one launch (what runs: qmm_ropekq_plan.h)
 
 extern "C" {
 
@@ -1166,6 +1167,19 @@ int qmm_rope_kv_store(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * po
     GlueArgs g;
     g.q = q; g.pos = pos; g.ff = ff; g.qd = q_dst; g.k = k; g.kd = k_dst; g.v = v; g.vd = v_dst;
     return run_glue(ctx, ctx->s(stream), glue_rope_kv_store_plan(q, k, v, v_dst), g);
+}
+
+int qmm_rope_kq_store_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
+                                const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst) {
+    return ropekq_takes_store(q, pos, ff, q_dst, k, k_dst, v, v_dst);
+}
+
+int qmm_rope_kq_store(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
+                      const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst, void * stream) {
+    if (!ctx || !ropekq_takes_store(q, pos, ff, q_dst, k, k_dst, v, v_dst)) return fail(QMM_EUNSUPPORTED, "qmm_rope_kq_store: operands not supported");
+    HIP_TRY(hipSetDevice(ctx->device));
+    QMM_CHAIN_FLUSH(ctx);
+    return ropekq_store(ctx, ctx->s(stream), q, pos, ff, q_dst, k, k_dst, v, v_dst);
 }
 
 int qmm_moe_router_supported(const qmm_tensor * logits, const qmm_tensor * ids, const qmm_tensor * weights, int64_t n_used) {

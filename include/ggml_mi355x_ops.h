@@ -130,11 +130,24 @@ QMM_API int qmm_attn_prefill(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tens
 /* What follows the q / k / v projections of a few-token batch in build_attn (src/llama-graph.cpp:1306-1365), in one launch:
  *   q_dst = rope(q) (f32; q_dst carries the ROPE node's op_params), k_dst = (f16) rope(k) straight into the K cache view,
  *   v_dst = (f16) v into the (transposed) V cache view, element i of v (in v's index order) to element i of v_dst, as CPY does.
- * k / k_dst and v / v_dst are optional pairs (NULL).  A Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 k_dst is refused: a quantized
- * K cache is stored by ROPE and QMM_OP_CPY. */
+ * k / k_dst and v / v_dst are optional pairs (NULL).  A Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 k_dst is refused here: a quantized
+ * K cache is stored by qmm_rope_kq_store below, or by ROPE and QMM_OP_CPY. */
 QMM_API int qmm_rope_kv_store_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
                                         const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst);
 QMM_API int qmm_rope_kv_store(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
+                              const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst, void * stream);
+
+/* The same on a quantized K cache (-ctk q8_0 / q4_0 / q4_1 / q5_0 / q5_1), any batch size, in one launch: q, pos, ff, q_dst and the optional
+ * pair v / v_dst as above (modes normal and NEOX, n_dims <= D, YaRN parameters in q_dst->op_params).  k is required: f32 [D, H_kv, N], dense
+ * rows, 4-byte strides and data, D % 32 == 0, D * H_kv <= 8192, ne[0] / ne[2] / ne[3] agreeing with q.  k_dst is required: type 8, 2, 3, 6 or
+ * 7, k's extents, contiguous in that type's blocks, data on a 2-byte boundary.  Everything else is refused: an F16 k_dst (qmm_rope_kv_store
+ * takes it), IQ4_NL and every other type, rows of partial blocks, a non-contiguous k_dst.
+ *   q_dst, v_dst  bit for bit what qmm_rope_kv_store(q, pos, ff, q_dst, NULL, NULL, v, v_dst) writes
+ *   k_dst         byte for byte what QMM_OP_ROPE (k -> a contiguous f32 tensor, q_dst's op_params) followed by QMM_OP_CPY (-> k_dst) writes:
+ *                 Q8_0 blocks in the context's act mode, the other four as quantize_row_*_ref; no byte outside its blocks is written */
+QMM_API int qmm_rope_kq_store_supported(const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
+                                        const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst);
+QMM_API int qmm_rope_kq_store(qmm_ctx * ctx, const qmm_tensor * q, const qmm_tensor * pos, const qmm_tensor * ff, const qmm_tensor * q_dst,
                               const qmm_tensor * k, const qmm_tensor * k_dst, const qmm_tensor * v, const qmm_tensor * v_dst, void * stream);
 
 /* The router of a mixture-of-experts block behind its logits (build_moe_ffn, src/llama-graph.cpp:818-858) as one launch:
